@@ -24,7 +24,8 @@ consecutive steps process different reads and genomic windows (a stream, not one
 = one pass of the engine over every call of one block (Stage2_compute on its own stream, the DP launch
 classes on three more).  The timed steps stream the blocks as two pipelines, the stage-2 chains and the DP
 classes, each block's work complete inside the timed region (GMAPDP_BENCH_PIPE=0: each step joined at its
-end; its time is reported beside the headline as step_split_ms.together_serial).  Inputs (descriptors, query arenas, splice
+end; with --full its time is reported beside the headline as step_split_ms.together_serial).  Inputs
+(descriptors, query arenas, splice
 probabilities) are resident in HBM before the timed region (the contract's `value`); the host plans
 (bands, launch classes) are made once per block and their cost is reported as plan_ms.
 
@@ -37,6 +38,15 @@ status; under torch.distributed.run the ranks come from the environment.  One pr
 (backend nccl) for the barrier and the max-over-ranks step time only: the path has no exchange step.
 `--dry-run` runs the launcher, the process group (gloo), the block sharding and the workload generation on
 the CPU without a GPU (tests/test_bench_launcher.py).
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the headline
+line: metric, value, unit, ms_per_step (milliseconds per timed step), dtype, the workload and the host's
+setup times.  `--full` goes on from there as the line's other figures need: the serialised step and its
+stage-2 / DP legs, every block's output checks, per-kernel times and rooflines, PCIe and the compact pair
+stream, the pipelined loop and the CPU baselines (the reference's own objects, tools/cpu_baseline.py), all
+in the same line.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs below); the inputs are seeded, so two builds run with the same arguments can be compared
+output for output.
 """
 import argparse
 import ctypes as C
@@ -406,7 +416,8 @@ def make_stream(args, rank, world):
     t0 = time.perf_counter()
     genome = W.PackedGenome(layout.total, seed=38)
     W.plant_stream(genome, layout, args.reads, range(world * args.batches), shape)
-    workers = int(os.environ.get("GMAPDP_BENCH_WORKERS", "0")) or max(1, min(args.batches, 16 // world))
+    # (a worker makes one part of a block at a time, workload.PARTS: three parts per block)
+    workers = int(os.environ.get("GMAPDP_BENCH_WORKERS", "0")) or max(1, min(3 * args.batches, 16 // world))
     data = W.make_blocks(genome, layout, args.reads, mine, shape=shape, sprob=False, workers=workers)
     if args.config == 1:  # configs[1] times the single and end gaps alone
         for d in data:
@@ -459,7 +470,15 @@ def main():
     ap.add_argument("--mix", default="d", choices=["d", "appb"],
                     help="per-read call mix: d = measured with the reference's gmap -d (stage 1 included; 1.585 "
                          "Stage2_compute calls per read over ~214-kb windows), appb = SURVEY App. B (rounds 1-3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and report everything beside the headline: the serialised "
+                         "step and its stage-2 / DP legs, per-kernel times and rooflines, output checks, PCIe and the "
+                         "compact pair stream, the pipelined loop, and the CPU baselines (without it: set up, warm "
+                         "up, time --steps steps, print the headline line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (results and pairs of its block, as a caller of the "
+                         "path receives them; seeded samples of the large arrays) to DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--dry-run", action="store_true", help="CPU only: launcher, gloo process group, sharding")
     ap.add_argument("--iso-kernel", default=None,
                     help="profiling mode: run only this kernel template's launch classes, one launch at a time on one "
@@ -573,7 +592,9 @@ def main():
     d_res = torch.zeros(max(mx("ngpu"), 1) * 32, dtype=torch.uint8, device=dev)
     d_gres = torch.zeros(max(mx("nggpu"), 1) * 72, dtype=torch.uint8, device=dev)
     d_pairs = torch.empty(max(mx("cap"), 1) * 16, dtype=torch.uint8, device=dev)
-    d_s2res = torch.zeros(args.reads * 32, dtype=torch.uint8, device=dev)
+    # (one record per Stage2_compute call: a block has more calls than reads)
+    s2res_bytes = max(max(len(b["d"]["oligo"]) for b in B), 1) * gmapdp.STAGE2_RESULT_DTYPE.itemsize
+    d_s2res = torch.zeros(s2res_bytes, dtype=torch.uint8, device=dev)
     d_mres = torch.zeros(max(max(len(b["d"]["microexon"]) for b in B), 1) * gmapdp.MICROEXON_RESULT_DTYPE.itemsize,
                          dtype=torch.uint8, device=dev)
     d_mpairs = torch.empty(max(mx("mcap"), 1) * 16, dtype=torch.uint8, device=dev)
@@ -607,8 +628,9 @@ def main():
     # two streams (measured slower: DESIGN.md §7).
     pipe = int(os.environ.get("GMAPDP_BENCH_PIPE", "3"))
     ostream2 = torch.cuda.Stream(dev) if pipe == 2 else None
-    d_s2res2 = torch.zeros(args.reads * 32, dtype=torch.uint8, device=dev) if pipe == 2 else None
+    d_s2res2 = torch.zeros(s2res_bytes, dtype=torch.uint8, device=dev) if pipe == 2 else None
     nstep = [0]
+    last_s2res = [d_s2res]  # the stage-2 result buffer the latest step wrote
     side_of = lambda k: min(k, len(sides))  # noqa: E731  plan stream k >= 1 -> side index + 1
 
     def launch(b, li, s, kernel_only=False):
@@ -648,6 +670,7 @@ def main():
         nstep[0] += 1
         os_, ss_, res = (ostream2, ostream2, d_s2res2) if alt else (ostream, sstream, None)
         if do_oligo:
+            last_s2res[0] = d_s2res if res is None else res
             if not (piped and pipe == 3):
                 ss_.wait_event(fork)
             if ev is not None:
@@ -814,6 +837,107 @@ def main():
         s2res = np.frombuffer(d_s2res.cpu().numpy().tobytes(), dtype=gmapdp.STAGE2_RESULT_DTYPE)[:len(op)]
         return stage2_algorithmic_bytes(op, ores, s2res)
 
+    def host_record():
+        """the host's per-block planning (gmapdp_plan_create_all, gmapdp_stage2_plan_create: 16 host threads),
+        the median block's (the first block also pays the process's first device allocations: listed apart)"""
+        return {"plan_ms_per_block": float(np.median(plan_ms)), "stage2_plan_ms_per_block": float(np.median(oplan_ms)),
+                "plan_ms_first_block": plan_ms[0], "stage2_plan_ms_first_block": oplan_ms[0],
+                "plan_threads": int(os.environ.get("GMAPDP_PLAN_THREADS", "16")),
+                "setup_s": t_gen}
+
+    def dump_outputs(b, path, rows=20000, calls=200, max_pairs=200000):
+        """--dump-outputs: what a caller of the timed path receives from the step that just ran block b, as
+        float64 tables (one column per field of the records, characters as their codes), in problem order:
+          dp_results / genome_results / microexon_results: the records of a seeded sample of `rows` problems
+            (<family>_problems: which), dp = single gaps then end gaps; stage2_results: every call's;
+          <family>_pairs: the pair records of the sampled problems, in order, whole problems up to `max_pairs`
+            records; stage2_path_lengths / stage2_path_pairs: of a sample of `calls` Stage2_compute calls.
+        Offsets into the arenas (where the records lie, not what they say) are left out.  The sample is
+        the same in every run, and so are the inputs: two builds can be compared file by file."""
+        os.makedirs(path, exist_ok=True)
+        rng = np.random.default_rng(20240222)
+        written = []
+
+        def pick(n, k):
+            if n == 0:
+                return np.zeros(0, dtype=np.int64)
+            return np.sort(rng.choice(n, size=min(n, k), replace=False)).astype(np.int64)
+
+        def save(name, rec):
+            cols = [np.ascontiguousarray(rec[f]) for f in rec.dtype.names if not f.endswith(("_offset", "_"))]
+            arr = np.stack([(c.view(np.uint8) if c.dtype.kind == "S" else c).astype(np.float64) for c in cols], axis=1)
+            np.save(os.path.join(path, name + ".npy"), arr)
+            written.append(arr.nbytes)
+
+        def save_plain(name, values):
+            arr = np.asarray(values, dtype=np.float64)
+            np.save(os.path.join(path, name + ".npy"), arr)
+            written.append(arr.nbytes)
+
+        def records(d_arena, dtype, offs, cnts):
+            """the records [offs[i], offs[i] + cnts[i]) of a device arena, whole lists while they fit max_pairs"""
+            cnts = np.maximum(np.asarray(cnts, dtype=np.int64), 0)
+            fit = np.cumsum(cnts) <= max_pairs
+            offs, cnts = np.asarray(offs, dtype=np.int64)[fit], cnts[fit]
+            idx = np.repeat(offs, cnts) + (np.arange(int(cnts.sum())) - np.repeat(np.cumsum(cnts) - cnts, cnts))
+            raw = d_arena.view(-1, dtype.itemsize)[torch.from_numpy(idx).to(dev)].cpu().numpy()
+            return np.frombuffer(raw.tobytes(), dtype=dtype)
+
+        torch.cuda.synchronize()
+        res, gres = fetch_results(b)
+        # single and end gaps, genome gaps: a problem's record is on the device (dev_index) or, where the host
+        # answered at plan time, in the plan's host results
+        for name, n, index, dres, hres in (
+                ("dp", b["ns"] + b["ne"], lib.gmapdp_plan_dev_index, res, b["host_res"]),
+                ("genome", b["ng"], lib.gmapdp_plan_genome_dev_index, gres, b["host_gres"])):
+            sel = pick(n, rows)
+            di = np.array([index(b["plan"], int(i)) for i in sel], dtype=np.int64)
+            rec = hres[sel].copy()
+            rec[di >= 0] = dres[di[di >= 0]]
+            save_plain(name + "_problems", sel)
+            save(name + "_results", rec)
+            on = rec[di >= 0]
+            save(name + "_pairs", records(d_pairs, gmapdp.PAIR_DTYPE, on["pair_offset"], on["npairs"]))
+        mp = b["d"]["microexon"]
+        if b["mplan"] is not None:
+            mres = np.frombuffer(d_mres.cpu().numpy().tobytes(), dtype=gmapdp.MICROEXON_RESULT_DTYPE)[:len(mp)]
+            sel = pick(len(mp), rows)
+            save_plain("microexon_problems", sel)
+            save("microexon_results", mres[sel])
+            save("microexon_pairs", records(d_mpairs, gmapdp.PAIR_DTYPE, mres[sel]["pair_offset"], mres[sel]["npairs"]))
+        if b["oplan"] is not None:
+            n = len(b["d"]["oligo"])
+            s2r = np.zeros(n, dtype=gmapdp.STAGE2_RESULT_DTYPE)
+            pn, qn = C.c_size_t(), C.c_size_t()
+            fetch = lambda paths, pairs: lib.gmapdp_stage2_plan_fetch(  # noqa: E731
+                eng.h, b["oplan"], C.c_void_p(last_s2res[0].data_ptr()), C.c_void_p(stream.cuda_stream), s2r.ctypes.data,
+                paths.ctypes.data if paths is not None else None, len(paths) if paths is not None else 0,
+                pairs.ctypes.data if pairs is not None else None, len(pairs) if pairs is not None else 0,
+                C.byref(pn), C.byref(qn))
+            rc = fetch(None, None)  # sizes first (GMAPDP_ESPACE, -6, with the counts needed)
+            if rc not in (0, -6):
+                eng._check(rc, "gmapdp_stage2_plan_fetch")
+            paths = np.zeros(max(pn.value, 1), dtype=gmapdp.PATH_DTYPE)
+            ppairs = np.zeros(max(qn.value, 1), dtype=gmapdp.PATH_PAIR_DTYPE)
+            eng._check(fetch(paths, ppairs), "gmapdp_stage2_plan_fetch")
+            save("stage2_results", s2r)
+            sel = pick(n, calls)
+            sel = sel[s2r[sel]["nresults"] > 0]
+            pc = s2r[sel]["nresults"].astype(np.int64)  # a call's paths: nresults records from paths[path_offset]
+            pi = np.repeat(s2r[sel]["path_offset"].astype(np.int64), pc) + (np.arange(int(pc.sum()))
+                                                                            - np.repeat(np.cumsum(pc) - pc, pc))
+            mine_paths = paths[pi]
+            save_plain("stage2_calls", sel)
+            save_plain("stage2_path_lengths", mine_paths["npairs"])
+            cnt = np.maximum(mine_paths["npairs"].astype(np.int64), 0)
+            fit = np.cumsum(cnt) <= max_pairs
+            cnt, off = cnt[fit], mine_paths["pair_offset"][fit]
+            qi = np.repeat(off, cnt) + (np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+            save("stage2_path_pairs", ppairs[qi])
+        assert sum(written) <= 64 << 20, "bench: --dump-outputs wrote %d bytes" % sum(written)
+        progress("outputs of block %d's step written to %s (%d files, %.1f MB)"
+                 % (b["id"], path, len(written), sum(written) / 1e6))
+
     if args.iso_kernel:
         if args.iso_kernel in S2_WHAT:
             if not all(b["oplan"] is not None for b in B):
@@ -847,6 +971,79 @@ def main():
     progress("timing %d steps over %d blocks" % (args.steps, len(B)))
     elapsed, evs = timed(args.steps, args.warmup)
     progress("headline %.2f ms per step" % (elapsed / args.steps * 1e3))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(B[(args.steps - 1) % len(B)], args.dump_outputs)
+
+    ms_step = elapsed / args.steps * 1e3
+    reads_total = args.reads * world * args.steps
+    nsub = {k: int(np.mean([len(b["d"][k]) for b in B])) for k in ("oligo", "single", "end", "genome", "microexon")}
+    nsub_end3 = float(np.mean([int((b["d"]["end"]["end3p"] != 0).sum()) for b in B]))
+    nsub_end5 = nsub["end"] - nsub_end3
+    out = {
+        "metric": METRIC,
+        "value": reads_total / elapsed,
+        "unit": "reads/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int16/int8 saturating (SIMD-build semantics)" if args.simd else "int32",
+        "data": "synthetic",
+        "full": bool(args.full),
+        "config": {"workload": "configs[%d]: synthetic %d-nt %s reads (%d exons x %d nt, %g %% subs, %g %% indels) vs a "
+                               "%s-layout i.i.d. genome (%d chromosomes, %d nt, universal coordinates to %d): per read "
+                               "%.3g Stage2_compute calls (seeding + chaining, locus +- %d-nt windows) + %.1f "
+                               "Dynprog_single_gap + %.1f "
+                               "Dynprog_end5_gap + %.1f Dynprog_end3_gap + %.1f Dynprog_genome_gap + %.1f "
+                               "Dynprog_microexon_int (%s semantics)%s; %d distinct blocks of %d reads cycled per rank; "
+                               "inputs HBM-resident; host stages 1/3 not in the step"
+                               % (args.config, shape.readlength, "Iso-Seq-style" if args.config == 4 else "cDNA",
+                                  shape.exons, shape.exlen, 100 * shape.subs, 100 * shape.indel, gname,
+                                  len(layout.lens), layout.total, layout.total - 1, nsub["oligo"] / args.reads,
+                                  shape.pad, nsub["single"] / args.reads,
+                                  nsub_end5 / args.reads, nsub_end3 / args.reads, nsub["genome"] / args.reads,
+                                  nsub["microexon"] / args.reads, "gmap.avx2" if args.simd else "nosimd",
+                                  " -- Dynprog_single + Dynprog_end only, as configs[1] names it" if args.config == 1
+                                  else "", len(B), args.reads),
+                   "genome": gname, "reads_per_step_per_gpu": args.reads, "blocks_per_rank": len(B),
+                   "call_mix_source": shape.source,
+                   "subproblems_per_step_per_gpu": {"stage2_compute": nsub["oligo"], "single": nsub["single"],
+                                                    "end": nsub["end"], "genome": nsub["genome"],
+                                                    "microexon": nsub["microexon"]},
+                   "parallelism": "dp%d (reads sharded by rank, --part=r/%d over read blocks; genome replicated)"
+                                  % (world, world)},
+    }
+
+    def close_out():
+        """the shard record (every rank's blocks, checked disjoint and complete), the rank's own line, and
+        the plans released"""
+        out["shard"] = shard.gather_blocks(mine, [b["d"]["reads"] for b in B], dist if world > 1 else None)
+        rank_line = {"rank": rank, "world_size": dist.get_world_size() if world > 1 else 1,
+                     "backend": dist.get_backend() if world > 1 else None, "device": local,
+                     "blocks": mine, "ms_per_step_local": ms_step}
+        err_line(json.dumps({"rank_line": rank_line}))
+        for b in B:
+            lib.gmapdp_plan_destroy(b["plan"])
+            if b["oplan"] is not None:
+                lib.gmapdp_stage2_plan_destroy(b["oplan"])
+            if b["mplan"] is not None:
+                lib.gmapdp_microexon_plan_destroy(b["mplan"])
+
+    if not args.full:
+        # the plain run ends here: the headline and what it cost the host to set up
+        out["block_runs"] = dict(block_runs)
+        out["host"] = host_record()
+        close_out()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything beside the headline ----
     el_serial, _ = timed(args.steps, 1, piped=False)
     half = max(2, args.steps // 4)
     el_dp, _ = timed(half, 1, do_oligo=False)
@@ -1166,47 +1363,8 @@ def main():
         del slots
         progress("pipelined with PCIe: %.2f ms per step" % pipelined["ms_per_step"])
 
-    ms_step = elapsed / args.steps * 1e3
-    reads_total = args.reads * world * args.steps
-    nsub = {k: int(np.mean([len(b["d"][k]) for b in B])) for k in ("oligo", "single", "end", "genome", "microexon")}
-    nsub_end3 = float(np.mean([int((b["d"]["end"]["end3p"] != 0).sum()) for b in B]))
-    nsub_end5 = nsub["end"] - nsub_end3
-    out = {
-        "metric": METRIC,
-        "value": reads_total / elapsed,
-        "unit": "reads/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int16/int8 saturating (SIMD-build semantics)" if args.simd else "int32",
-        "data": "synthetic",
-        "config": {"workload": "configs[%d]: synthetic %d-nt %s reads (%d exons x %d nt, %g %% subs, %g %% indels) vs a "
-                               "%s-layout i.i.d. genome (%d chromosomes, %d nt, universal coordinates to %d): per read "
-                               "%.3g Stage2_compute calls (seeding + chaining, locus +- %d-nt windows) + %.1f "
-                               "Dynprog_single_gap + %.1f "
-                               "Dynprog_end5_gap + %.1f Dynprog_end3_gap + %.1f Dynprog_genome_gap + %.1f "
-                               "Dynprog_microexon_int (%s semantics)%s; %d distinct blocks of %d reads cycled per rank; "
-                               "inputs HBM-resident; host stages 1/3 not in the step"
-                               % (args.config, shape.readlength, "Iso-Seq-style" if args.config == 4 else "cDNA",
-                                  shape.exons, shape.exlen, 100 * shape.subs, 100 * shape.indel, gname,
-                                  len(layout.lens), layout.total, layout.total - 1, nsub["oligo"] / args.reads,
-                                  shape.pad, nsub["single"] / args.reads,
-                                  nsub_end5 / args.reads, nsub_end3 / args.reads, nsub["genome"] / args.reads,
-                                  nsub["microexon"] / args.reads, "gmap.avx2" if args.simd else "nosimd",
-                                  " -- Dynprog_single + Dynprog_end only, as configs[1] names it" if args.config == 1
-                                  else "", len(B), args.reads),
-                   "genome": gname, "reads_per_step_per_gpu": args.reads, "blocks_per_rank": len(B),
-                   "call_mix_source": shape.source,
-                   "subproblems_per_step_per_gpu": {"stage2_compute": nsub["oligo"], "single": nsub["single"],
-                                                    "end": nsub["end"], "genome": nsub["genome"],
-                                                    "microexon": nsub["microexon"]},
-                   "banded_cells_per_step_per_gpu": cells_total // len(B),
-                   "parallelism": "dp%d (reads sharded by rank, --part=r/%d over read blocks; genome replicated)"
-                                  % (world, world)},
+    out["config"]["banded_cells_per_step_per_gpu"] = cells_total // len(B)
+    out.update({
         "roofline": {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
                      "traffic": traffic, "traffic_source": psrc, "kernel": dominant,
                      "kernel_ms_per_launch": kms, "algorithmic_bytes_per_launch": kbytes,
@@ -1253,12 +1411,7 @@ def main():
         "block_runs": dict(block_runs),
         "launch_classes": sorted(({"kernel": n, "dispatches": e[1], "ms_per_step": round(e[0] / args.steps, 4)}
                                   for n, e in per_kernel.items()), key=lambda x: -x["ms_per_step"]),
-        # the host's per-block planning (gmapdp_plan_create_all, gmapdp_stage2_plan_create: 16 host threads),
-        # the median block's (the first block also pays the process's first device allocations: listed apart)
-        "host": {"plan_ms_per_block": float(np.median(plan_ms)), "stage2_plan_ms_per_block": float(np.median(oplan_ms)),
-                 "plan_ms_first_block": plan_ms[0], "stage2_plan_ms_first_block": oplan_ms[0],
-                 "plan_threads": int(os.environ.get("GMAPDP_PLAN_THREADS", "16")),
-                 "setup_s": t_gen},
+        "host": host_record(),
         "checks": {"pairs_per_read": checks["pairs"] / checks["reads"],
                    "genome_gaps_bridged": checks["genome_gaps_bridged"],
                    "genome_gap_simple": checks["genome_gap_simple"],
@@ -1266,19 +1419,8 @@ def main():
                    "stage2_path_pairs_per_read": checks["stage2_path_pairs"] / checks["reads"],
                    "microexon_candidates": checks["microexon_candidates"],
                    "microexons_found": checks["microexons_found"], "reads_checked": checks["reads"]},
-    }
-    # shard record: every rank's blocks, checked disjoint and complete
-    out["shard"] = shard.gather_blocks(mine, [b["d"]["reads"] for b in B], dist if world > 1 else None)
-    rank_line = {"rank": rank, "world_size": dist.get_world_size() if world > 1 else 1,
-                 "backend": dist.get_backend() if world > 1 else None, "device": local,
-                 "blocks": mine, "ms_per_step_local": ms_step}
-    err_line(json.dumps({"rank_line": rank_line}))
-    for b in B:
-        lib.gmapdp_plan_destroy(b["plan"])
-        if b["oplan"] is not None:
-            lib.gmapdp_stage2_plan_destroy(b["oplan"])
-        if b["mplan"] is not None:
-            lib.gmapdp_microexon_plan_destroy(b["mplan"])
+    })
+    close_out()
     if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config in (1, 2) and not args.simd:
         progress("CPU baselines")
         cb = cpu_baselines(args.mix, args.config)

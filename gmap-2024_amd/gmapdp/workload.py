@@ -184,6 +184,28 @@ class PackedGenome:
         np.bitwise_and.at(self.blocks, w, ~(np.uint32(3) << sh))
         np.bitwise_or.at(self.blocks, w, code << sh)
 
+    def plant_runs(self, start, chars):
+        """Write the rows of `chars` (n x L ASCII, L <= 32) at the universal positions start[i] ..
+        start[i] + L - 1.  No two rows may touch the same 32-nt block (plant_sites sees to that), so each
+        row is packed once (2 bits per nt) and lands as whole words: at most two blocks, two words each."""
+        n, L = chars.shape
+        val = np.zeros(n, dtype=np.uint64)
+        for m in range(L):
+            val |= CODE[chars[:, m]].astype(np.uint64) << np.uint64(2 * m)
+        mask = np.uint64((1 << (2 * L)) - 1)
+        start = np.asarray(start, dtype=np.int64)
+        blk = start >> 5
+        off = ((start & 31) << 1).astype(np.uint64)
+        up = np.uint64(63) - off  # the part past the block's 64 bits, shifted in two steps (off may be 0)
+        low32 = np.uint64(0xFFFFFFFF)
+        for b, v, k in ((blk, val << off, mask << off),
+                        (blk + 1, (val >> up) >> np.uint64(1), (mask >> up) >> np.uint64(1))):
+            # nt 0-15 of a block are its second word, nt 16-31 its first
+            for w, v32, k32 in ((3 * b + 1, v & low32, k & low32), (3 * b, v >> np.uint64(32), k >> np.uint64(32))):
+                sel = np.flatnonzero(k32)
+                ws = w[sel]
+                self.blocks[ws] = (self.blocks[ws] & ~k32[sel].astype(np.uint32)) | v32[sel].astype(np.uint32)
+
     def ascii(self, start, end):
         """bytes of universal positions [start, end) (whole blocks through a byte -> 4-nt table; the
         stream has no flagged positions below `length`)"""
@@ -361,11 +383,33 @@ def plant_sites(genome, st):
     x, y = st["goffL"] + st["a"], st["revR"] - st["b"]   # first / last intron base, strand coordinates
     don, acc = splice_pool()
     dc, ac = don[st["dctx"]], acc[st["actx"]]
+    runs = [(x - 3, dc), (y - 19, ac)]   # (strand position of the context's first base, contexts)
+    slow = [slice(None), slice(None)]    # the contexts written position by position, in order
+    if isinstance(genome, PackedGenome):
+        # Packed genome: a context that shares no 32-nt block with another is written as whole words
+        # (PackedGenome.plant_runs).  The few that do go position by position afterwards, in the order
+        # below, so where two contexts overlap the later write stays, as before.
+        first = [np.where(watson, choff + p, chrhigh - (p + c.shape[1] - 1)) for p, c in runs]
+        b0 = np.concatenate(first) >> 5
+        b1 = np.concatenate([f + c.shape[1] - 1 for f, (_, c) in zip(first, runs)]) >> 5
+        order = np.argsort(b0, kind="stable")
+        hit = b0[order][1:] <= np.maximum.accumulate(b1[order])[:-1]
+        shared = np.zeros(len(b0), dtype=bool)
+        shared[order[1:]] |= hit
+        shared[order[:-1]] |= hit
+        n = len(x)
+        for k, (f, (_, c)) in enumerate(zip(first, runs)):
+            alone = np.flatnonzero(~shared[k * n:(k + 1) * n])
+            # in universal order a minus-strand context runs backwards, complemented
+            cc = c[alone]
+            genome.plant_runs(f[alone], np.where(watson[alone, None], cc, COMPL[cc][:, ::-1]))
+            slow[k] = np.flatnonzero(shared[k * n:(k + 1) * n])
     idx, ch = [], []
-    ctx = [(x + k - 3, dc[:, k]) for k in range(9)] + [(y + k - 19, ac[:, k]) for k in range(23)]
-    for pos, c in ctx:
-        idx.append(np.where(watson, choff + pos, chrhigh - pos))
-        ch.append(np.where(watson, c, COMPL[c]).astype(np.uint8))
+    for (p, c), s in zip(runs, slow):
+        for k in range(c.shape[1]):
+            pos, ck = p[s] + k, c[s, k]
+            idx.append(np.where(watson[s], choff[s] + pos, chrhigh[s] - pos))
+            ch.append(np.where(watson[s], ck, COMPL[ck]).astype(np.uint8))
     genome[np.concatenate(idx)] = np.concatenate(ch)
 
 
@@ -497,26 +541,34 @@ def block_seeds(b):
     return 1000 + 7919 * b, 23 + b
 
 
-def make_reads(genome, layout, reads, seed, site_seed=23, shape=CDNA2K, plant=True, sprob=True):
-    """The per-read call stream of `reads` reads of `shape`: dict of descriptor arrays and arenas.
-    With `plant`, genome gaps plant their intron motifs first (in place), then every other sub-problem
-    is cut."""
-    rng = np.random.default_rng(seed)
-    ng = int(round(reads * shape.genome))
-    # intron sites are rank-independent (site_seed), so every rank plants the same genome
-    gp, gq, sp = make_genome_gaps(genome, layout, ng, np.random.default_rng(seed + 1), site_seed=site_seed,
-                                  plant=plant, sprob=sprob)
-    ns = int(round(reads * shape.single))
-    n5 = int(round(reads * shape.end5))
-    n3 = int(round(reads * shape.end3))
-    sp_, sq = make_single(genome, layout, ns, rng, shape)
-    ep, eq = make_end(genome, layout, n5, n3, rng)
+PARTS = ("genome", "ends", "stage2")  # the independently seeded parts of a block's call stream
+
+
+def make_part(genome, layout, reads, seed, part, site_seed=23, shape=CDNA2K, plant=True, sprob=True):
+    """One of PARTS of the call stream make_reads returns (each has its own generator, so they can be
+    made in any order or side by side): "genome" -> (genome gaps, queries, splice probabilities),
+    "ends" -> (single gaps, queries, end gaps, queries), "stage2" -> (Stage2_compute calls, queries)."""
+    if part == "genome":
+        # intron sites are rank-independent (site_seed), so every rank plants the same genome
+        return make_genome_gaps(genome, layout, int(round(reads * shape.genome)), np.random.default_rng(seed + 1),
+                                site_seed=site_seed, plant=plant, sprob=sprob)
+    if part == "ends":
+        rng = np.random.default_rng(seed)
+        ns = int(round(reads * shape.single))
+        n5 = int(round(reads * shape.end5))
+        n3 = int(round(reads * shape.end3))
+        return make_single(genome, layout, ns, rng, shape) + make_end(genome, layout, n5, n3, rng)
+    return make_stage2(genome, layout, reads, np.random.default_rng(seed + 3), exons=shape.exons,
+                       exlen=shape.exlen, pad=shape.pad, subs=shape.subs, indel=shape.indel,
+                       extra=shape.stage2 - 1.0)
+
+
+def join_parts(parts, reads, seed, shape=CDNA2K, sprob=True):
+    """The call stream of a block from its PARTS (make_part's results, in PARTS order)."""
+    (gp, gq, sp), (sp_, sq, ep, eq), (op, oq) = parts
     ep["qoff"] += len(sq)
     gp["qoff"] += len(sq) + len(eq)
     q = np.concatenate([sq, eq, gq])
-    op, oq = make_stage2(genome, layout, reads, np.random.default_rng(seed + 3), exons=shape.exons,
-                         exlen=shape.exlen, pad=shape.pad, subs=shape.subs, indel=shape.indel,
-                         extra=shape.stage2 - 1.0)
     mp = make_microexon(gp, int(round(reads * shape.microexon)), np.random.default_rng(seed + 4))
     out = {"single": sp_, "end": ep, "genome": gp, "q": q, "oligo": op, "oq": oq, "microexon": mp,
            "reads": reads}
@@ -527,6 +579,15 @@ def make_reads(genome, layout, reads, seed, site_seed=23, shape=CDNA2K, plant=Tr
     return out
 
 
+def make_reads(genome, layout, reads, seed, site_seed=23, shape=CDNA2K, plant=True, sprob=True):
+    """The per-read call stream of `reads` reads of `shape`: dict of descriptor arrays and arenas.
+    With `plant`, genome gaps plant their intron motifs first (in place), then every other sub-problem
+    is cut."""
+    parts = [make_part(genome, layout, reads, seed, part, site_seed=site_seed, shape=shape, plant=plant, sprob=sprob)
+             for part in PARTS]
+    return join_parts(parts, reads, seed, shape=shape, sprob=sprob)
+
+
 def plant_stream(genome, layout, reads, blocks, shape=CDNA2K):
     """Plant the intron sites of every block of the stream, in block order (every rank does the same,
     so every rank holds the same genome)."""
@@ -534,10 +595,11 @@ def plant_stream(genome, layout, reads, blocks, shape=CDNA2K):
         plant_sites(genome, genome_gap_sites(layout, int(round(reads * shape.genome)), block_seeds(b)[1]))
 
 
-def _block_worker(args):
-    genome, layout, reads, b, shape, sprob = _POOL_STATE[0], _POOL_STATE[1], args[0], args[1], args[2], args[3]
+def _part_worker(args):
+    genome, layout = _POOL_STATE[0], _POOL_STATE[1]
+    reads, b, shape, sprob, part = args
     seed, site_seed = block_seeds(b)
-    return make_reads(genome, layout, reads, seed, site_seed=site_seed, shape=shape, plant=False, sprob=sprob)
+    return make_part(genome, layout, reads, seed, part, site_seed=site_seed, shape=shape, plant=False, sprob=sprob)
 
 
 _POOL_STATE = [None, None]
@@ -545,14 +607,19 @@ _POOL_STATE = [None, None]
 
 def make_blocks(genome, layout, reads, blocks, shape=CDNA2K, sprob=True, workers=1):
     """The call streams of `blocks` (the genome already planted by plant_stream), generated in
-    `workers` forked processes (the genome is shared copy-on-write; call before any GPU work)."""
+    `workers` forked processes (the genome is shared copy-on-write; call before any GPU work).  The unit
+    of work is one of a block's PARTS, the longest ("genome") handed out first."""
     _POOL_STATE[0], _POOL_STATE[1] = genome, layout
-    jobs = [(reads, b, shape, sprob) for b in blocks]
+    jobs = [(reads, b, shape, sprob, part) for part in PARTS for b in blocks]
     try:
-        if workers <= 1 or len(blocks) <= 1:
-            return [_block_worker(j) for j in jobs]
-        import multiprocessing as mp
-        with mp.get_context("fork").Pool(min(workers, len(blocks))) as pool:
-            return pool.map(_block_worker, jobs)
+        if workers <= 1:
+            done = [_part_worker(j) for j in jobs]
+        else:
+            import multiprocessing as mp
+            with mp.get_context("fork").Pool(min(workers, len(jobs))) as pool:
+                done = pool.map(_part_worker, jobs, chunksize=1)
     finally:
         _POOL_STATE[0] = _POOL_STATE[1] = None
+    nb = len(blocks)
+    return [join_parts([done[k * nb + i] for k in range(len(PARTS))], reads, block_seeds(b)[0], shape=shape,
+                       sprob=sprob) for i, b in enumerate(blocks)]

@@ -69,6 +69,40 @@ def test_stream_blocks_independent_of_world_size():
         assert np.array_equal(outs[0][1][k], outs[1][1][k]), k
 
 
+def test_packed_planting_matches_ascii_planting():
+    """plant_sites on the packed genome (whole-word writes of the contexts that share no 32-nt block, the
+    others position by position) leaves what planting the same sites base by base into an ASCII copy
+    leaves, on a layout crowded enough that many contexts share blocks or overlap."""
+    from gmapdp import workload as W
+    layout = W.Layout([("a", 300000), ("b", 200001)])
+    g = W.PackedGenome(layout.total, seed=7)
+    flat = np.frombuffer(g.ascii(0, layout.total), dtype=np.uint8).copy()
+    shared = 0
+    for seed in (23, 24):   # the second round writes over the first's sites
+        st = W.genome_gap_sites(layout, 3000, seed)
+        W.plant_sites(g, st)
+        W.plant_sites(flat, st)
+        x = np.where(st["watson"], st["choff"] + st["goffL"] + st["a"], st["chrhigh"] - st["goffL"] - st["a"])
+        shared += len(x) - len(np.unique(x >> 5))
+    assert shared > 100
+    assert g.ascii(0, layout.total) == flat.tobytes()
+    assert np.all(g.blocks[-4:] == 0xFFFFFFFF)
+
+
+def test_blocks_same_from_worker_processes():
+    """make_blocks hands a block's parts to worker processes: the blocks are the ones one process makes."""
+    from gmapdp import workload as W
+    layout = W.Layout(W.CHR22)
+    g = W.PackedGenome(layout.total, seed=38)
+    W.plant_stream(g, layout, 60, range(2), W.CDNA2K)
+    one = W.make_blocks(g, layout, 60, [0, 1], sprob=False)
+    many = W.make_blocks(g, layout, 60, [0, 1], sprob=False, workers=3)
+    for a, b in zip(one, many):
+        assert sorted(a) == sorted(b)
+        for k in a:
+            assert np.array_equal(a[k], b[k]), k
+
+
 def test_isoseq_reads_shape():
     """configs[4] read shape: 10 exons x 500 nt with 1 % indels gives ragged queries near 5 kb."""
     from gmapdp import workload as W

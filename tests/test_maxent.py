@@ -80,6 +80,26 @@ def test_maxent_table_binary_layout():
     assert len(raw) == 16 + 16 * 40 + 8 * (12 * 16384 + 4 * 16)
 
 
+def test_maxent_fixtures_make_the_built_tables():
+    """The stored model weights (tests/golden/maxent_hr_{plus,minus}.npz, what a checkout without the reference
+    tree builds the tables from) give the table binary the build left next to the library, byte for byte -- so
+    where the build parsed the reference's source, the fixtures agree with that source."""
+    import sys
+    if not os.path.exists(TABLES):
+        pytest.skip("maxent tables not generated")
+    tool = os.path.join(ROOT, "tools", "make_maxent_tables.py")
+    sys.path.insert(0, os.path.dirname(tool))
+    try:
+        import make_maxent_tables as M
+    finally:
+        sys.path.pop(0)
+    tables = M.read_golden()
+    assert tables is not None and sorted(tables) == sorted(n for n, _ in M.TABLES)
+    body = b"".join(n.encode().ljust(32, b"\0") + np.array([k, 0], dtype="<u4").tobytes()
+                    + np.array(tables[n], dtype="<f8").tobytes() for n, k in M.TABLES)
+    assert open(TABLES, "rb").read() == M.MAGIC + np.array([len(M.TABLES), 0], dtype="<u4").tobytes() + body
+
+
 def test_bench_splice_pool_is_strong_and_diverse():
     """The bench plants these contexts at its genome-gap introns (workload.splice_pool): every one is a strong
     site under MaxEnt (>= 0.9, the oracle restatement), and they are distinct (no 8-mer is planted millions of

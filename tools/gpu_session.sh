@@ -3,10 +3,10 @@
 # limit, the session ends at the first failure.  Outputs under gpurun_out/<tag>/.
 #   tests          the whole -m gpu suite
 #   tests:<k>      the -m gpu tests matching -k <k>
-#   bench:<lib>    bench.py --steps 20 --no-cpu-baseline with gmap-2024_amd/<lib>/libgmapdp.so
-#   bx:<tag>:<args>  bench.py --steps 10 --no-cpu-baseline <args> -> bx_<tag>.json
-#   benchfull      bench.py as the driver runs it (CPU baseline included)
-#   simd:<lib>     bench.py --simd;  c4:<lib>  bench.py --config 4
+#   bench:<lib>    bench.py --full --steps 20 --no-cpu-baseline with gmap-2024_amd/<lib>/libgmapdp.so
+#   bx:<tag>:<args>  bench.py --full --steps 10 --no-cpu-baseline <args> -> bx_<tag>.json
+#   benchfull      bench.py --full (every figure of the line, CPU baselines included)
+#   simd:<lib>     bench.py --full --simd;  c4:<lib>  bench.py --full --config 4
 #   iso:<kernel>   tools/profile.sh <tag>_iso iso <kernel>  (the dominant kernel's launches alone)
 #   prof           tools/profile.sh <tag>  (kernel stats + PMC passes of the bench step)
 #   smoke          __graft_entry__.smoke()
@@ -26,12 +26,12 @@ for S in "$@"; do
   case "$S" in
     tests) timeout -k 10 900 python -u -m pytest -x -v --timeout 300 --timeout-method thread -m gpu tests > $O/gputest.txt 2>&1 || exit 11 ;;
     tests:*) timeout -k 10 900 python -u -m pytest -x -v --timeout 300 --timeout-method thread -m gpu -k "${S#tests:}" tests > $O/gputest_k.txt 2>&1 || exit 12 ;;
-    bench:*) L=${S#bench:}; GMAPDP_LIB=$PWD/gmap-2024_amd/$L/libgmapdp.so timeout -k 10 400 python bench.py --steps 20 --no-cpu-baseline > $O/bench_$L.json 2> $O/bench_$L.err || exit 13 ;;
-    bp:*) L=${S#bp:}; GMAPDP_BENCH_S2_PRIORITY=1 GMAPDP_LIB=$PWD/gmap-2024_amd/$L/libgmapdp.so timeout -k 10 400 python bench.py --steps 20 --no-cpu-baseline > $O/bp_$L.json 2> $O/bp_$L.err || exit 27 ;;
-    simd:*) L=${S#simd:}; GMAPDP_LIB=$PWD/gmap-2024_amd/$L/libgmapdp.so timeout -k 10 400 python bench.py --steps 20 --simd --no-cpu-baseline > $O/simd_$L.json 2> $O/simd_$L.err || exit 14 ;;
-    c4:*) L=${S#c4:}; GMAPDP_LIB=$PWD/gmap-2024_amd/$L/libgmapdp.so timeout -k 10 600 python bench.py --steps 10 --config 4 --no-cpu-baseline > $O/c4_$L.json 2> $O/c4_$L.err || exit 15 ;;
-    bx:*) X=${S#bx:}; T=${X%%:*}; A=${X#*:}; timeout -k 10 600 python bench.py --steps 10 --no-cpu-baseline $A > $O/bx_$T.json 2> $O/bx_$T.err || exit 23 ;;
-    benchfull) timeout -k 10 900 python bench.py > $O/bench.json 2> $O/bench.err || exit 16 ;;
+    bench:*) L=${S#bench:}; GMAPDP_LIB=$PWD/gmap-2024_amd/$L/libgmapdp.so timeout -k 10 400 python bench.py --full --steps 20 --no-cpu-baseline > $O/bench_$L.json 2> $O/bench_$L.err || exit 13 ;;
+    bp:*) L=${S#bp:}; GMAPDP_BENCH_S2_PRIORITY=1 GMAPDP_LIB=$PWD/gmap-2024_amd/$L/libgmapdp.so timeout -k 10 400 python bench.py --full --steps 20 --no-cpu-baseline > $O/bp_$L.json 2> $O/bp_$L.err || exit 27 ;;
+    simd:*) L=${S#simd:}; GMAPDP_LIB=$PWD/gmap-2024_amd/$L/libgmapdp.so timeout -k 10 400 python bench.py --full --steps 20 --simd --no-cpu-baseline > $O/simd_$L.json 2> $O/simd_$L.err || exit 14 ;;
+    c4:*) L=${S#c4:}; GMAPDP_LIB=$PWD/gmap-2024_amd/$L/libgmapdp.so timeout -k 10 600 python bench.py --full --steps 10 --config 4 --no-cpu-baseline > $O/c4_$L.json 2> $O/c4_$L.err || exit 15 ;;
+    bx:*) X=${S#bx:}; T=${X%%:*}; A=${X#*:}; timeout -k 10 600 python bench.py --full --steps 10 --no-cpu-baseline $A > $O/bx_$T.json 2> $O/bx_$T.err || exit 23 ;;
+    benchfull) timeout -k 10 900 python bench.py --full > $O/bench.json 2> $O/bench.err || exit 16 ;;
     iso:*) bash tools/profile.sh ${TAG}_iso iso "${S#iso:}" > $O/prof_iso.txt 2>&1 || exit 17 ;;
     prof) bash tools/profile.sh $TAG > $O/prof.txt 2>&1 || exit 18 ;;
     profs2) bash tools/profile_s2.sh ${TAG}_s2 > $O/profs2.txt 2>&1 || exit 30 ;;

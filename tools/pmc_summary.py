@@ -111,7 +111,7 @@ def main(src, dst, iso=False):
     summary = {
         "recorded": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime()),  # bench.py selects summaries by this
         "workload": workload_of(src),  # ... and only those of its own workload
-        "command": "python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline %s(under rocprofv3, tools/profile.sh)"
+        "command": "python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline %s(under rocprofv3, tools/profile.sh)"
                    % (open(os.path.join(src, "bench_args.txt")).read().strip() + " "
                       if os.path.exists(os.path.join(src, "bench_args.txt")) else ""),
         "hbm_bytes_rule": "2*FETCH_SIZE + WRITE_SIZE, KB -> bytes x1024 (MI355X_MICROARCH.md HBM: gfx950 "

@@ -39,7 +39,7 @@ if [ "$MODE" = iso ] || [ "$MODE" = isosimd ]; then
   echo done
   exit 0
 fi
-BENCH=(python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline "${SIMD[@]}")
+BENCH=(python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline "${SIMD[@]}")
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- "${BENCH[@]}" > $OUT/stats.log 2>&1 || exit 1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- "${BENCH[@]}" > $OUT/fetch.log 2>&1 || exit 2
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o run -- "${BENCH[@]}" > $OUT/write.log 2>&1 || exit 3
