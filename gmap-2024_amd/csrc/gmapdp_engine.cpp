@@ -32,6 +32,7 @@
 
 #include "gmapdp_internal.h"
 #include "me_device.h"
+#include "pc_expand.h"
 #include "../../include/gmapdp.h"
 
 namespace gmapdp {
@@ -2740,57 +2741,18 @@ int gmapdp_plan_run_launch(gmapdp_ctx* ctx, const gmapdp_plan* plan, int li, con
 }  // extern "C"
 
 // (Rec: gmapdp_pair, 17-B RAW ops, or gmapdp_path_pair, 21-B RAW ops; list i: npairs_of(i) records at
-// offset_of(i))
+// offset_of(i) of out's `capacity` records; the per-list decoder is pc_expand.h's)
 template <typename Rec, typename NP, typename OF>
 static int expand_stream(const uint8_t* stream, const uint64_t* offsets, int n, NP&& npairs_of, OF&& offset_of,
-                         Rec* out, int nthreads) {
-  static const char nt[4] = {'A', 'C', 'G', 'T'}, cp[4] = {'*', '|', ' ', ':'};
-  constexpr int kRaw = 1 + (int)sizeof(Rec);
+                         Rec* out, size_t capacity, int nthreads) {
   const int T = nthreads > 0 ? nthreads : plan_threads((size_t)n * 64);
   std::vector<int> bad_at(T, -1);
   plan_parallel((size_t)n, T, [&](size_t lo, size_t hi, int t) {
     for (size_t i = lo; i < hi; i++) {
-      const uint8_t* p = stream + offsets[i];
-      const uint8_t* end = stream + offsets[i + 1];
       const int m = std::max<int>(npairs_of(i), 0);
-      Rec* o = m ? out + offset_of(i) : out;
-      int k = 0;
-      while (k < m && p < end) {
-        if (*p == 0x02) {
-          if (end - p < kRaw) break;
-          std::memcpy(&o[k++], p + 1, sizeof(Rec));
-          p += kRaw;
-          continue;
-        }
-        if (*p != 0x01 || end - p < 13) break;
-        int32_t q, g;
-        std::memcpy(&q, p + 1, 4);
-        std::memcpy(&g, p + 5, 4);
-        const int dq = (int8_t)p[9], dg = (int8_t)p[10];
-        const int len = p[11] | (p[12] << 8);
-        p += 13;
-        for (int r = 0; r < len && k < m && p < end; r++, k++) {
-          Rec& x = o[k];
-          x.querypos = q + r * dq;
-          x.genomepos = g + r * dg;
-          if constexpr (sizeof(Rec) == sizeof(gmapdp_pair)) {
-            x.jump = 0;
-          } else {
-            x.queryjump = 0;
-            x.genomejump = 0;
-          }
-          if (*p == 0xFF) {
-            std::memcpy(&x.cdna, p + 1, 4);
-            p += 5;
-          } else {
-            const uint8_t b = *p++;
-            x.cdna = nt[b & 3];
-            x.genome = x.genomealt = nt[(b >> 2) & 3];
-            x.comp = cp[(b >> 4) & 3];
-          }
-        }
-      }
-      if (k != m || p != end) {
+      const int64_t at = m ? (int64_t)offset_of(i) : 0;
+      if (offsets[i] > offsets[i + 1] || at < 0 || (uint64_t)at > capacity || (uint64_t)m > capacity - (uint64_t)at ||
+          !gmapdp::pc_expand_list(stream + offsets[i], stream + offsets[i + 1], out + at, m)) {
         bad_at[t] = (int)i;
         return;
       }
@@ -2804,34 +2766,57 @@ static int expand_stream(const uint8_t* stream, const uint64_t* offsets, int n, 
 extern "C" {
 
 int gmapdp_expand_pairs(const uint8_t* stream, const uint64_t* offsets, int n, const int32_t* npairs,
-                        const int64_t* pair_offsets, gmapdp_pair* out, int nthreads) {
+                        const int64_t* pair_offsets, gmapdp_pair* out, size_t capacity, int nthreads) {
   if (n < 0 || (n && (!stream || !offsets || !npairs || !pair_offsets || !out))) return GMAPDP_EINVAL;
   return expand_stream(stream, offsets, n, [&](size_t i) { return npairs[i]; },
-                       [&](size_t i) { return pair_offsets[i]; }, out, nthreads);
+                       [&](size_t i) { return pair_offsets[i]; }, out, capacity, nthreads);
 }
 
 int gmapdp_expand_path_pairs(const uint8_t* stream, const uint64_t* offsets, int npaths, const gmapdp_path* paths,
-                             gmapdp_path_pair* out, int nthreads) {
+                             gmapdp_path_pair* out, size_t capacity, int nthreads) {
   if (npaths < 0 || (npaths && (!stream || !offsets || !paths || !out))) return GMAPDP_EINVAL;
   return expand_stream(stream, offsets, npaths, [&](size_t i) { return paths[i].npairs; },
-                       [&](size_t i) { return paths[i].pair_offset; }, out, nthreads);
+                       [&](size_t i) { return paths[i].pair_offset; }, out, capacity, nthreads);
+}
+
+// The compact pair stream (pc_kernel.hip) of caller-made lists: n gmapdp_result records then ng
+// gmapdp_genome_result records (device), each naming npairs records at pair_offset of d_pairs.
+size_t gmapdp_compact_bound(size_t nrecords, int is_path_pairs) {
+  return (is_path_pairs ? 21 : 18) * nrecords + 64;
+}
+int gmapdp_compact_pairs(gmapdp_ctx* ctx, const gmapdp_result* d_results, int n, const gmapdp_genome_result* d_gresults,
+                         int ng, const gmapdp_pair* d_pairs, uint8_t* d_out, uint64_t* d_offsets, void* stream) {
+  if (!ctx || !d_offsets || n < 0 || ng < 0 || (n && !d_results) || (ng && !d_gresults)) return GMAPDP_EINVAL;
+  if ((int64_t)n + ng > INT32_MAX) return bad(ctx, "pair compaction: too many lists");
+  (void)hipSetDevice(ctx->device);
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  const hipError_t e = launch_pc((const unsigned char*)d_results, n, (int)sizeof(gmapdp_result),
+                                 (const unsigned char*)d_gresults, ng, (int)sizeof(gmapdp_genome_result), d_pairs,
+                                 (unsigned long long*)d_offsets, (unsigned char*)d_out, s);
+  return e == hipSuccess ? GMAPDP_OK : fail(ctx, GMAPDP_ELAUNCH, "pair compaction: %s", e);
+}
+int gmapdp_compact_path_pairs(gmapdp_ctx* ctx, const gmapdp_path* d_paths, const uint64_t* d_npaths, size_t path_cap,
+                              const gmapdp_path_pair* d_pairs, size_t pair_cap, uint8_t* d_out, uint64_t* d_offsets,
+                              void* stream) {
+  if (!ctx || !d_offsets || (path_cap && (!d_paths || !d_npaths))) return GMAPDP_EINVAL;
+  if (path_cap > (size_t)INT32_MAX) return bad(ctx, "path pair compaction: too many path records");
+  (void)hipSetDevice(ctx->device);
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  const hipError_t e = launch_pc_paths(d_paths, (const unsigned long long*)d_npaths, (int)path_cap, d_pairs, pair_cap,
+                                       (unsigned long long*)d_offsets, (unsigned char*)d_out, s);
+  return e == hipSuccess ? GMAPDP_OK : fail(ctx, GMAPDP_ELAUNCH, "path pair compaction: %s", e);
 }
 
 // The compact pair stream (pc_kernel.hip): the plan's GPU problems in dev-slot order, then its genome gaps.
 size_t gmapdp_plan_compact_bound(const gmapdp_plan* plan) {
-  return plan ? 17 * plan->in.pair_capacity + 64 : 0;
+  return plan ? gmapdp_compact_bound(plan->in.pair_capacity, 0) : 0;
 }
 int gmapdp_plan_compact_pairs(gmapdp_ctx* ctx, const gmapdp_plan* plan, const gmapdp_result* d_results,
                               const gmapdp_pair* d_pairs, uint8_t* d_out, uint64_t* d_offsets, void* stream) {
   if (!ctx || !plan || !d_offsets || (!plan->in.dev.empty() && !d_results)) return GMAPDP_EINVAL;
   if (!plan->in.gdev.empty() && !plan->d_gresults) return bad(ctx, "genome-gap results not bound");
-  (void)hipSetDevice(ctx->device);
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  const hipError_t e = launch_pc((const unsigned char*)d_results, (int)plan->in.dev.size(), (int)sizeof(gmapdp_result),
-                                 (const unsigned char*)plan->d_gresults, (int)plan->in.gdev.size(),
-                                 (int)sizeof(gmapdp_genome_result), d_pairs, (unsigned long long*)d_offsets,
-                                 (unsigned char*)d_out, s);
-  return e == hipSuccess ? GMAPDP_OK : fail(ctx, GMAPDP_ELAUNCH, "pair compaction: %s", e);
+  return gmapdp_compact_pairs(ctx, d_results, (int)plan->in.dev.size(), plan->d_gresults, (int)plan->in.gdev.size(),
+                              d_pairs, d_out, d_offsets, stream);
 }
 
 int gmapdp_plan_run_launch_kernel(gmapdp_ctx* ctx, const gmapdp_plan* plan, int li, const char* d_qseq,
@@ -4249,17 +4234,13 @@ int gmapdp_stage2_plan_fetch(gmapdp_ctx* ctx, const gmapdp_stage2_plan* plan, co
 // The compact stream of the plan's path pairs (pc_kernel.hip), one list per path record of the pool
 size_t gmapdp_stage2_plan_compact_bound(const gmapdp_stage2_plan* plan, size_t* path_cap) {
   if (path_cap) *path_cap = plan ? plan->path_cap : 0;
-  return plan ? 21 * plan->pair_cap + 64 : 0;
+  return plan ? gmapdp_compact_bound(plan->pair_cap, 1) : 0;
 }
 int gmapdp_stage2_plan_compact_pairs(gmapdp_ctx* ctx, const gmapdp_stage2_plan* plan, uint8_t* d_out,
                                      uint64_t* d_offsets, void* stream) {
   if (!ctx || !plan || !d_offsets) return GMAPDP_EINVAL;
-  if (plan->path_cap > (size_t)INT32_MAX) return bad(ctx, "stage-2 compaction: too many path records");
-  (void)hipSetDevice(ctx->device);
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  const hipError_t e = launch_pc_paths(plan->d_paths, plan->d_counters + 1, (int)plan->path_cap, plan->d_pairs,
-                                       plan->pair_cap, (unsigned long long*)d_offsets, (unsigned char*)d_out, s);
-  return e == hipSuccess ? GMAPDP_OK : fail(ctx, GMAPDP_ELAUNCH, "path pair compaction: %s", e);
+  return gmapdp_compact_path_pairs(ctx, plan->d_paths, (const uint64_t*)(plan->d_counters + 1), plan->path_cap,
+                                   plan->d_pairs, plan->pair_cap, d_out, d_offsets, stream);
 }
 
 int gmapdp_stage2_plan_seeding_classes(const gmapdp_stage2_plan* plan, int* n16, int* n32) {

@@ -18,7 +18,9 @@
 // One wave per call, 64 records per step.  Record i continues the current run when neither it nor record i - 1
 // is RAW, its step from i - 1 is within [-1, 1]^2, and either that step equals the step into i - 1 or i - 1
 // had no step (it starts the list or follows a RAW record): every run's records then share the step of its
-// second record, with no sequential decision.  A run's length and step are written when its end is seen
+// second record, with no sequential decision.  A run holds at most 65 535 records (its length is a uint16):
+// the record that would be its 65 536th starts a new run with a header of its own, although it continues, and
+// the records after it continue that one.  A run's length and step are written when its end is seen
 // (possibly a step later).  The first launch (WRITE = false) sizes every call's stream; a one-workgroup scan
 // turns the sizes into offsets; the second writes.
 #include "dp_device.h"
@@ -27,6 +29,7 @@ namespace gmapdp {
 
 constexpr unsigned char kPcRun = 0x01, kPcRaw = 0x02, kPcEsc = 0xFF;
 constexpr int kPcHeader = 13;
+constexpr int kPcMaxRun = 65535;
 
 __device__ __forceinline__ int pc_nt(char c) {
   return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1;
@@ -111,6 +114,9 @@ __global__ __launch_bounds__(64) void pc_kernel(Src P, unsigned long long* __res
   int pq = 0, pg = 0, praw = 1, pdq = 0, pdg = 0, pstep = 0;
   long long hdr = -1;  // the open run's header offset (WRITE), -1: none
   int runlen = 0, rdq = 0, rdg = 0;
+  // only a list of more than kPcMaxRun records can hold a run that reaches the cap; for every other list the
+  // sizing pass needs no run bookkeeping (wave-uniform)
+  const bool longlist = npairs > kPcMaxRun;
   for (int c0 = 0; c0 < npairs; c0 += 64) {
     const int k = c0 + lane;
     const bool v = k < npairs;
@@ -137,14 +143,20 @@ __global__ __launch_bounds__(64) void pc_kernel(Src P, unsigned long long* __res
       s1v = c0 == 0 ? 0 : pstep;
     }
     const bool cont = stepok && (!s1v || (dq == s1q && dg == s1g));
-    const bool start = v && !raw && !cont;
+    // run ends: the open run (from an earlier step, or a lane below) closes at the first record that does not
+    // continue it, or that would be its record kPcMaxRun + 1 (only a run open from an earlier step can be that
+    // long: at most one such lane per step, below the first non-continuing one; runlen is wave-uniform)
+    uint64_t sm = ballot(v && !cont);                   // records that begin a run or are RAW
+    bool capped = false;
+    if (longlist) {
+      capped = v && runlen > 0 && runlen + lane == kPcMaxRun && lane < (sm ? __ffsll((long long)sm) - 1 : 64);
+      sm |= ballot(capped);
+    }
+    const bool start = v && !raw && (!cont || capped);
     const int code = v && !raw ? pc_code(ch) : 0;
     const int bytes = !v ? 0 : raw ? Src::kRaw : (start ? kPcHeader : 0) + (code < 0 ? 5 : 1);
     const int incl = wave_scan_add(lane, bytes);
     const unsigned long long at = pos + (unsigned long long)(incl - bytes);
-    // run ends: the open run (from an earlier step, or a lane below) closes at the first record that does not
-    // continue it
-    const uint64_t sm = ballot(v && !cont);            // records that begin a run or are RAW
     if (WRITE) {
       if (raw) {
         o[at] = kPcRaw;
@@ -170,8 +182,9 @@ __global__ __launch_bounds__(64) void pc_kernel(Src P, unsigned long long* __res
         }
       }
     }
-    // run bookkeeping (wave-uniform): a run ends just before the next record that does not continue it
-    {
+    // run bookkeeping (wave-uniform): a run ends just before the next record that does not continue it (the
+    // sizing pass needs the open run's length only where the cap can fall)
+    if (WRITE || longlist) {
       uint64_t starts = ballot(start);
       // the run open from the previous step continues through this step's lanes before its first
       // non-continuing record

@@ -297,10 +297,16 @@ def load_library(path=LIB_PATH):
         "gmapdp_plan_compact_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]),
         "gmapdp_expand_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_int]),
+                                          C.c_size_t, C.c_int]),
+        "gmapdp_compact_bound": (C.c_size_t, [C.c_size_t, C.c_int]),
+        "gmapdp_compact_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+        "gmapdp_compact_path_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
         "gmapdp_stage2_plan_compact_bound": (C.c_size_t, [C.c_void_p, P(C.c_size_t)]),
         "gmapdp_stage2_plan_compact_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-        "gmapdp_expand_path_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+        "gmapdp_expand_path_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                               C.c_int]),
         "gmapdp_maxent_sites": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
         "gmapdp_microexon_plan_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                    C.c_size_t, P(C.c_void_p)]),
@@ -809,7 +815,8 @@ class Engine:
         run_qucbuf when given: another query of the same layout), gmapdp_stage2_plan_fetch.  Returns
         (results, paths, pairs, (calls with 16-bit, with 32-bit seeding counters)).  compact_out (a dict):
         also the compact stream of the path pairs (gmapdp_stage2_plan_compact_pairs) expanded on the host
-        (gmapdp_expand_path_pairs): compact_out["pairs"] (an arena like `pairs`), ["bytes"]."""
+        (gmapdp_expand_path_pairs): compact_out["pairs"] (an arena like `pairs`), ["bytes"], ["bound"]
+        (gmapdp_stage2_plan_compact_bound)."""
         lib, n = self.lib, len(probs)
         hip = _hip()
         plan = C.c_void_p()
@@ -861,6 +868,7 @@ class Engine:
                     raise GmapdpError("hipMemcpy failed")
                 compact_out["pairs"] = expand_path_pairs(stream, offs, paths[:pn.value], max(qn.value, 1))
                 compact_out["bytes"] = int(offs[-1])
+                compact_out["bound"] = int(bound)
             return results, paths[:pn.value], pairs[:qn.value], (n16.value, n32.value)
         finally:
             for b in bufs:
@@ -1083,7 +1091,7 @@ def expand_pairs(stream, offsets, npairs, pair_offsets, capacity, nthreads=0):
     npc = np.ascontiguousarray(npairs, dtype=np.int32)
     po = np.ascontiguousarray(pair_offsets, dtype=np.int64)
     rc = lib.gmapdp_expand_pairs(st.ctypes.data, of.ctypes.data, len(npc), npc.ctypes.data, po.ctypes.data,
-                                 out.ctypes.data, int(nthreads))
+                                 out.ctypes.data, len(out), int(nthreads))
     if rc != 0:
         raise GmapdpError("gmapdp_expand_pairs: the stream does not decode to the records (%d)" % rc)
     return out
@@ -1099,7 +1107,7 @@ def expand_path_pairs(stream, offsets, paths, capacity, nthreads=0):
     of = np.ascontiguousarray(offsets, dtype=np.uint64)
     pa = np.ascontiguousarray(paths, dtype=PATH_DTYPE)
     rc = lib.gmapdp_expand_path_pairs(st.ctypes.data, of.ctypes.data, len(pa), pa.ctypes.data, out.ctypes.data,
-                                      int(nthreads))
+                                      len(out), int(nthreads))
     if rc != 0:
         raise GmapdpError("gmapdp_expand_path_pairs: the stream does not decode to the records (%d)" % rc)
     return out

@@ -686,13 +686,21 @@ int gmapdp_stage2_plan_seeding_classes (const gmapdp_stage2_plan *plan, int *n16
  * ops: gmapdp_path_pair records with a jump or a negative position): one list per record of the plan's path
  * pool (*path_cap of them; records past the pool's count are empty lists).  d_offsets: path_cap + 1 uint64
  * (device), exclusive offsets and the total; d_out NULL sizes only, else at least
- * gmapdp_stage2_plan_compact_bound bytes.  gmapdp_expand_path_pairs restores the records on the host, each
- * path's npairs at its pair_offset (the path records as gmapdp_stage2_plan_fetch returns them). */
+ * gmapdp_stage2_plan_compact_bound bytes (21 B per record of the pair pool, + 64).  gmapdp_expand_path_pairs
+ * restores the records on the host, each path's npairs at its pair_offset of out's `capacity` records (the
+ * path records as gmapdp_stage2_plan_fetch returns them); GMAPDP_EINVAL as gmapdp_expand_pairs. */
 size_t gmapdp_stage2_plan_compact_bound (const gmapdp_stage2_plan *plan, size_t *path_cap);
 int gmapdp_stage2_plan_compact_pairs (gmapdp_ctx *ctx, const gmapdp_stage2_plan *plan, uint8_t *d_out,
                                       uint64_t *d_offsets, void *stream);
 int gmapdp_expand_path_pairs (const uint8_t *stream, const uint64_t *offsets, int npaths, const gmapdp_path *paths,
-                              gmapdp_path_pair *out, int nthreads);
+                              gmapdp_path_pair *out, size_t capacity, int nthreads);
+/* The same over caller-made device buffers (gmapdp_stage2_plan_compact_pairs calls it with the plan's own):
+ * path_cap gmapdp_path records of which the first *d_npaths count (the others, and a path with a negative
+ * offset or count or with pair_offset + npairs > pair_cap, are empty lists); d_offsets: path_cap + 1 uint64;
+ * d_out NULL sizes only, else at least gmapdp_compact_bound (pair_cap, 1) bytes, or the sizing pass's total. */
+int gmapdp_compact_path_pairs (gmapdp_ctx *ctx, const gmapdp_path *d_paths, const uint64_t *d_npaths, size_t path_cap,
+                               const gmapdp_path_pair *d_pairs, size_t pair_cap, uint8_t *d_out, uint64_t *d_offsets,
+                               void *stream);
 void gmapdp_stage2_plan_destroy (gmapdp_stage2_plan *plan);
 
 /* Create a context on HIP device `device`.  mode = Mode_T (mode.h:5;
@@ -818,15 +826,26 @@ int gmapdp_plan_run (gmapdp_ctx *ctx, const gmapdp_plan *plan, const char *d_qse
  * each GPU problem's list (dev slots 0..gmapdp_plan_gpu_problems - 1, then the genome gaps' slots) becomes a
  * byte stream; d_offsets (gpu problems + genome gpu problems + 1 uint64, device) receives the exclusive
  * offsets and the total.  d_out NULL: the offsets only (to size a copy); else at least
- * gmapdp_plan_compact_bound bytes.  Stream format: pc_kernel.hip. */
+ * gmapdp_plan_compact_bound bytes: 18 B per record of the pair arena (a record that starts a run and whose
+ * characters need the escape takes 13 + 5 B), + 64.  Stream format: pc_kernel.hip. */
 size_t gmapdp_plan_compact_bound (const gmapdp_plan *plan);
 int gmapdp_plan_compact_pairs (gmapdp_ctx *ctx, const gmapdp_plan *plan, const gmapdp_result *d_results,
                                const gmapdp_pair *d_pairs, uint8_t *d_out, uint64_t *d_offsets, void *stream);
+/* The same over caller-made device buffers (gmapdp_plan_compact_pairs calls it with the plan's own): n
+ * gmapdp_result records then ng gmapdp_genome_result records, each a list of npairs (negative: none)
+ * records at pair_offset of d_pairs; d_offsets: n + ng + 1 uint64.  gmapdp_compact_bound: the most bytes
+ * the stream of nrecords records takes (18 B each, 21 B for path pairs, + 64). */
+size_t gmapdp_compact_bound (size_t nrecords, int is_path_pairs);
+int gmapdp_compact_pairs (gmapdp_ctx *ctx, const gmapdp_result *d_results, int n,
+                          const gmapdp_genome_result *d_gresults, int ng, const gmapdp_pair *d_pairs,
+                          uint8_t *d_out, uint64_t *d_offsets, void *stream);
 /* Host: problem i's ops (stream[offsets[i], offsets[i + 1])) back to its npairs[i] records at
- * out[pair_offsets[i]], on nthreads host threads (0: the plan builders' default).  GMAPDP_EINVAL when a
- * problem's ops do not decode to exactly its records. */
+ * out[pair_offsets[i]], on nthreads host threads (0: the plan builders' default); out holds `capacity`
+ * records.  GMAPDP_EINVAL when a problem's ops do not decode to exactly its records and bytes (nothing
+ * outside its ops is read), when its offsets decrease, or when its records do not lie inside out
+ * (pair_offsets[i] < 0 or pair_offsets[i] + npairs[i] > capacity); nothing outside out is written. */
 int gmapdp_expand_pairs (const uint8_t *stream, const uint64_t *offsets, int n, const int32_t *npairs,
-                         const int64_t *pair_offsets, gmapdp_pair *out, int nthreads);
+                         const int64_t *pair_offsets, gmapdp_pair *out, size_t capacity, int nthreads);
 /* Per-launch-class access (one kernel launch per class; for profiling). */
 int gmapdp_plan_launch_info (const gmapdp_plan *plan, int li, int *R, int *dirs_lds, int *count, size_t *lds);
 /* Launch classes are spread over the caller's stream (0) and three side streams (1..3),

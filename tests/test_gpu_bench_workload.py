@@ -235,6 +235,7 @@ def test_gpu_bench_configs2_stage2_every_call(grch38_block0):
         idx = np.repeat(ppaths["pair_offset"], cnt) + (np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt))
         assert len(idx) > 0 and np.array_equal(cmp["pairs"][idx], ppairs[idx]), \
             "the compact path-pair stream does not expand to the records"
+        assert cmp["bytes"] <= cmp["bound"]
         _progress("compact path-pair stream: %d records in %d bytes" % (len(idx), cmp["bytes"]))
     finally:
         eng.close()
@@ -313,6 +314,7 @@ def _dp_plan_block(eng, d, compact=False):
                 eng._check(lib.gmapdp_plan_compact_pairs(eng.h, plan, d_res, d_pairs, None, d_off, None), "compact")
                 assert hip.hipDeviceSynchronize() == 0
                 offs = down(np.zeros(nprob + 1, dtype=np.uint64), d_off)
+                assert int(offs[-1]) <= lib.gmapdp_plan_compact_bound(plan)
                 d_out = dbuf(int(offs[-1]))
                 eng._check(lib.gmapdp_plan_compact_pairs(eng.h, plan, d_res, d_pairs, d_out, d_off, None), "compact")
                 assert hip.hipDeviceSynchronize() == 0
