@@ -2704,6 +2704,52 @@ int gmapdp_plan_launch_members(const gmapdp_plan* plan, int li, int* problem_ind
   return GMAPDP_OK;
 }
 
+// The direction scratch launch li's members touch (read-only; sizes recomputed from the descriptors by the
+// classification's own rules, offsets as the plan baked them in): per member its [offset, offset + bytes),
+// 0, 0 for a member without scratch; a packed class (kSx, kDpx with its directions outside LDS) has one
+// region per launch, reported for its first member.  *offset / *bytes: the hull of them.
+int gmapdp_plan_launch_member_scratch(const gmapdp_plan* plan, int li, uint64_t* offsets, uint64_t* bytes,
+                                      uint64_t* offset, uint64_t* total_bytes) {
+  if (!plan || li < 0 || li >= (int)plan->in.launches.size()) return GMAPDP_EINVAL;
+  const PlanCore& in = plan->in;
+  const auto& L = in.launches[li];
+  const bool latency = in.dev.size() + in.gdev.size() <= latency_batch();
+  const size_t lds_dirs_max = gg_lds_dirs_max();
+  uint64_t lo = UINT64_MAX, hi = 0;
+  auto put = [&](int k, uint64_t o, uint64_t b) {
+    if (offsets) offsets[k] = b ? o : 0;
+    if (bytes) bytes[k] = b;
+    if (b) {
+      lo = std::min(lo, o);
+      hi = std::max(hi, o + b);
+    }
+  };
+  const bool genome = L.kind == PlanCore::kGenomeGap || L.kind == PlanCore::kUxg;
+  const bool packed = L.kind == PlanCore::kSx || (L.kind == PlanCore::kDpx && !L.dirs_lds);
+  for (int k = 0; k < L.count; k++) {
+    if (packed) {
+      const size_t nblocks = ((size_t)L.count + (64 / L.R) - 1) / (64 / L.R);
+      put(k, L.gdirs_offset, k == 0 ? (uint64_t)((nblocks * L.extra + 255) & ~(size_t)255) : 0);
+    } else if (genome) {
+      DevGenomeProblem d = in.gdev[in.gorder[L.first + k]];
+      put(k, (uint64_t)d.dirs_offset, classify_gdev(d, latency, lds_dirs_max).gdirs);
+    } else {
+      DevProblem d = in.dev[in.order[L.first + k]];
+      const uint64_t o = (uint64_t)d.dirs_offset;  // (classify_dev resets its copy's)
+      put(k, o, classify_dev(d, latency).gdirs);
+    }
+  }
+  if (offset) *offset = hi ? lo : 0;
+  if (total_bytes) *total_bytes = hi ? hi - lo : 0;
+  return GMAPDP_OK;
+}
+
+int gmapdp_plan_launch_scratch(const gmapdp_plan* plan, int li, uint64_t* offset, uint64_t* bytes) {
+  return gmapdp_plan_launch_member_scratch(plan, li, nullptr, nullptr, offset, bytes);
+}
+
+size_t gmapdp_plan_scratch_bytes(const gmapdp_plan* plan) { return plan ? plan->in.gdirs_bytes : 0; }
+
 int gmapdp_plan_run(gmapdp_ctx* ctx, const gmapdp_plan* plan, const char* d_qseq, const char* d_qseq_uc,
                     gmapdp_result* d_results, gmapdp_pair* d_pairs, void* stream) {
   if (!ctx || !plan) return GMAPDP_EINVAL;

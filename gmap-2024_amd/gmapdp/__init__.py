@@ -316,6 +316,10 @@ def load_library(path=LIB_PATH):
         "gmapdp_microexon_plan_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
         "gmapdp_microexon_plan_destroy": (None, [C.c_void_p]),
+        "gmapdp_plan_launch_scratch": (C.c_int, [C.c_void_p, C.c_int, P(C.c_uint64), P(C.c_uint64)]),
+        "gmapdp_plan_launch_member_scratch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, P(C.c_uint64),
+                                                        P(C.c_uint64)]),
+        "gmapdp_plan_scratch_bytes": (C.c_size_t, [C.c_void_p]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

@@ -659,8 +659,23 @@ int gmapdp_stage2_batch (gmapdp_ctx *ctx, const gmapdp_stage2_problem *problems,
  * `stream` against device-resident query arenas.  what: 1 seeding only, 2 chaining only (after a
  * seeding run), 3 both.  d_results: n entries in problem order; paths and pairs stay in the plan's
  * pools (gmapdp_stage2_plan_outputs: device pointers and the counters {scratch, paths, pairs} bytes /
- * records used); a result with status -2 did not fit them.  Profiling: what = 4, 8 or 16 re-runs one
- * chaining kernel alone (s2a, the s2b sweep, s2c) over the scratch of a previous full run. */
+ * records used); a result with status -2 did not fit them.
+ * Split chaining: what = 4, 8 or 16 runs one chaining kernel alone (s2a with its two ordering passes, the
+ * s2b sweep, s2c).  1, then 4, 8, 16 in that order (on one stream, or each ordered after the one before by
+ * an event) is a supported way to run the chain and gives exactly what = 3 gives: results, pools and pool
+ * counters (tests/test_gpu_bench_step.py; bench.py's timed step runs it so, on a plan that never made a
+ * full run).  s2a needs the seeding of the same query arenas before it, s2b that s2a, s2c that s2b; the
+ * pool counters restart with s2a and again with s2c, which alone appends to the pools.  One of them re-run
+ * alone (profiling) works over the scratch the previous phases of the same query left.
+ * In flight at once on one context: a stage-2 plan owns its seeding arenas, chaining scratch, pools and
+ * counters, so its runs may overlap any DP or microexon plan's runs (tested: block k + 1's chain beside block
+ * k's DP classes and microexon plan).  Runs of stage-2 plans are kept in order on one stream by bench.py and
+ * the tests; two runs of the same plan must be ordered (they share all of the above), and so must a run and
+ * a gmapdp_stage2_plan_fetch of the pools it writes.  A microexon plan likewise owns its candidate arena and
+ * runs beside a DP plan's launches (tested); two runs of the same plan must be ordered.  DP plans: see
+ * gmapdp_plan_run_launch.
+ * Creating a plan of any kind sizes the context's grow-only buffers and runs on the context's stream:
+ * create plans while no run is in flight on the context. */
 typedef struct gmapdp_stage2_plan gmapdp_stage2_plan;
 int gmapdp_stage2_plan_create (gmapdp_ctx *ctx, const gmapdp_stage2_problem *problems, int n, const char *qseq,
                                const char *qseq_uc, size_t qbytes, gmapdp_stage2_plan **plan);
@@ -855,6 +870,33 @@ int gmapdp_plan_launch_stream (const gmapdp_plan *plan, int li);
 int gmapdp_plan_launch_is_tail (const gmapdp_plan *plan, int li);
 /* Original problem indices of launch li (count entries, launch order). */
 int gmapdp_plan_launch_members (const gmapdp_plan *plan, int li, int *problem_indices);
+/* The context's direction scratch (spilled direction planes, bridge candidates; one grow-only buffer per
+ * context, the offsets into it baked into the plan) that launch li's members can touch: the byte range
+ * [*offset, *offset + *bytes) around them, 0, 0 when the launch uses none; gmapdp_plan_scratch_bytes is the
+ * plan's total.  A problem's region follows the problems before it in problem order, not in launch order, so
+ * the ranges of two launches usually interleave; what keeps launches apart is that their members' regions
+ * are disjoint: gmapdp_plan_launch_member_scratch gives each member's own region (count entries, launch
+ * order; 0, 0 for a member without scratch; a packed class -- kinds 2 and 3 -- has one region for the whole
+ * launch, reported at its first member).  Read-only: sizes are recomputed from the descriptors. */
+int gmapdp_plan_launch_scratch (const gmapdp_plan *plan, int li, uint64_t *offset, uint64_t *bytes);
+int gmapdp_plan_launch_member_scratch (const gmapdp_plan *plan, int li, uint64_t *offsets, uint64_t *bytes,
+                                       uint64_t *offset, uint64_t *total_bytes);
+size_t gmapdp_plan_scratch_bytes (const gmapdp_plan *plan);
+/* One launch on the caller's `stream` (gmapdp_plan_launch_stream names which of the caller's main and side
+ * streams the plan's schedule means it for; the caller forks the side streams from main and joins them
+ * back, as gmapdp_plan_run does with the context's own).  On one context:
+ *   - the launches of ONE plan may all be in flight at once, on any streams: their members' scratch regions,
+ *     result slots and pair ranges are disjoint, and a genome-gap class's MaxEnt prologue fills only its own
+ *     members' entries of the bound probability arena (it must precede that class's kernel on its stream);
+ *   - TWO DP plans (or two runs of one plan) must not be in flight together: every plan's regions start at
+ *     byte 0 of the same scratch.  Order them on a stream (bench.py: every block's launches are forked from
+ *     and joined into one stream);
+ *   - stage-2 and microexon plans' runs share nothing with it and may overlap it (see
+ *     gmapdp_stage2_plan_run);
+ *   - the scratch only grows, and gmapdp_plan_create* already grows it to what the plan needs, so a run never
+ *     does: plans of different sizes run in any order on one context.  Growing frees the old buffer, which
+ *     waits for the whole device, so create plans while no run is in flight on the context.
+ * tests/test_gpu_bench_step.py runs exactly this schedule against the oracle. */
 int gmapdp_plan_run_launch (gmapdp_ctx *ctx, const gmapdp_plan *plan, int li, const char *d_qseq,
                             const char *d_qseq_uc, gmapdp_result *d_results, gmapdp_pair *d_pairs, void *stream);
 /* The same launch's kernel alone: a genome-gap class's device-MaxEnt prologue is not re-run (the splice

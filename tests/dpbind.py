@@ -762,11 +762,12 @@ def oracle_stage2_batch(orc, probs, qbuf, qucbuf, nthreads=None):
     return scal, paths, pairs, pair_off
 
 
-def stage2_mismatches(results, paths, pairs, orc_out, index=None):
+def stage2_mismatches(results, paths, pairs, orc_out, index=None, records_only=False):
     """Calls whose engine outputs (gmapdp_stage2_batch / plan format: results, path records, 20-B pair
     records) differ from oracle_stage2_batch's: nresults, npaths, ncovered, status, the Diag_compute_bounds
     query bounds (status 2) and every kept path's pair records byte for byte.  index[i]: the oracle row of
-    engine call i (default i).  Returns [(engine call, what)]."""
+    engine call i (default i).  records_only: the result records alone (the kept paths' total record count
+    in place of their records), for results whose paths are no longer held.  Returns [(engine call, what)]."""
     import numpy as np
     scal, opaths, opairs, pair_off = orc_out
     pb = pairs.view(np.uint8).reshape(-1) if len(pairs) else np.zeros(0, dtype=np.uint8)
@@ -784,6 +785,10 @@ def stage2_mismatches(results, paths, pairs, orc_out, index=None):
             continue
         if int(r["status"]) == 2 and (int(r["diag_querystart"]), int(r["diag_queryend"])) != (int(o[4]), int(o[5])):
             bad.append((i, "query bounds"))
+            continue
+        if records_only:
+            if int(r["npairs"]) != sum(int(opaths[j, k, 1]) for k in range(int(r["nresults"]))):
+                bad.append((i, "npairs"))
             continue
         for k in range(int(r["nresults"])):
             pr = paths[int(r["path_offset"]) + k]

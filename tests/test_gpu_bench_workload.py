@@ -25,8 +25,11 @@ import gmapdp
 from gmapdp import workload as W
 import ctypes as C
 
-from dpbind import (S2B_PATHS, Oracle, call_end, call_single, dp_batch_mismatches, microexon_probs,
-                    oracle_dp_batch, oracle_splice_probs, oracle_stage2_batch, stage2_mismatches)
+from benchstep import oracle_dp_block as _oracle_dp_block
+from benchstep import oracle_stage2_block as _oracle_stage2_block
+from benchstep import stage2_problems as _stage2_problems
+from dpbind import (Oracle, call_end, call_single, dp_batch_mismatches, microexon_probs, oracle_splice_probs,
+                    stage2_mismatches)
 
 pytestmark = pytest.mark.gpu
 TAIL = 8192
@@ -170,40 +173,6 @@ def test_gpu_bench_configs1_block_sample():
     assert sum(1 for r in got["single"] if r[1]) > 0.5 * sizes["single"]   # the fills emit pairs
 
 
-def _stage2_problems(d):
-    op = d["oligo"]
-    s2p = np.zeros(len(op), dtype=gmapdp.STAGE2_PROBLEM_DTYPE)
-    for k in ("qoff", "querylength", "chrstart", "chrend", "chroffset", "chrhigh", "plusp"):
-        s2p[k] = op[k]
-    s2p["splicingp"] = 1       # GMAP's defaults, as bench.py passes them
-    s2p["maxintronlen"] = 500000
-    return s2p
-
-
-def _oracle_stage2_block(genome, s2p, q):
-    """orc_stage2_batch over every call, chromosome by chromosome (the oracle holds one chromosome at
-    chroffset 0; the outputs are chromosome-relative)."""
-    orc = Oracle()
-    n = len(s2p)
-    scal = np.zeros((n, 8), dtype=np.int32)
-    paths = np.zeros((n, S2B_PATHS, 2), dtype=np.int32)
-    parts, off, base = [], np.zeros(n + 1, dtype=np.int64), 0
-    for cho in sorted(set(int(x) for x in s2p["chroffset"])):
-        idx = np.nonzero(s2p["chroffset"] == cho)[0]
-        chh = int(s2p["chrhigh"][idx[0]])
-        orc.set_genome(genome.ascii(cho, min(genome.length, chh + TAIL)))
-        sub = s2p[idx].copy()
-        sub["chroffset"] = 0
-        sub["chrhigh"] = chh - cho
-        sc, pa, pr, po = oracle_stage2_batch(orc, sub, q, q)
-        _progress("oracle: %d calls at chroffset %d" % (len(idx), cho))
-        scal[idx], paths[idx] = sc, pa
-        off[idx] = base + po[:-1]
-        parts.append(pr[:20 * int(po[-1])])
-        base += int(po[-1])
-    return scal, paths, np.concatenate(parts), off
-
-
 def test_gpu_bench_configs2_stage2_every_call(grch38_block0):
     """Every Stage2_compute call of bench block 0 (15 850 calls over ~214-kb windows at GRCh38 coordinates),
     bit-exact against the oracle through both engine paths:
@@ -342,39 +311,6 @@ def _dp_plan_block(eng, d, compact=False):
     finally:
         for b in bufs:
             hip.hipFree(b)
-    return out
-
-
-def _oracle_dp_block(genome, d, fams, simd=False):
-    """orc_dp_batch over every call of the families, chromosome by chromosome (the oracle holds one
-    chromosome at chroffset 0; outputs are chromosome-relative): {family: (scal, dscal, pairs, pair_off)}
-    in problem order."""
-    orc = Oracle(simd=simd)
-    q = d["q"].tobytes()
-    out = {}
-    for fam in fams:
-        p = d[fam]
-        n = len(p)
-        scal = np.zeros((n, 16), dtype=np.int32)
-        dscal = np.zeros((n, 2), dtype=np.float64)
-        parts, pair_off, base = [], np.zeros(n + 1, dtype=np.int64), 0
-        order = np.zeros(n, dtype=np.int64)
-        for cho in sorted(set(int(x) for x in p["chroffset"])):
-            idx = np.nonzero(p["chroffset"] == cho)[0]
-            chh = int(p["chrhigh"][idx[0]])
-            orc.set_genome(genome.ascii(cho, min(genome.length, chh + TAIL)))
-            sub = p[idx].copy()
-            sub["chroffset"] = 0
-            sub["chrhigh"] = chh - cho
-            sc, ds, pr, po = oracle_dp_batch(orc, fam, sub, q, q)
-            scal[idx], dscal[idx] = sc, ds
-            pair_off[idx] = base + po[:-1]
-            parts.append(pr[:int(po[-1])])
-            base += int(po[-1])
-            order[idx] = 1
-        pair_off[n] = base
-        out[fam] = (scal, dscal, np.concatenate(parts) if parts else np.zeros(1, dtype=gmapdp.PAIR_DTYPE), pair_off)
-        _progress("oracle: every %s call (%d)" % (fam, n))
     return out
 
 
