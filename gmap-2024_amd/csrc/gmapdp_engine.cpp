@@ -3327,6 +3327,8 @@ int gmapdp_oligo_mappings_batch(gmapdp_ctx* ctx, const gmapdp_oligo_problem* pro
   if (e == hipSuccess) e = ctx->qseq_uc.ensure(qbytes);
   hipStream_t s = ctx->stream;
   if (e == hipSuccess) e = hipMemcpyAsync(ctx->qseq_uc.p, qseq_uc, qbytes, hipMemcpyHostToDevice, s);
+  // (the kernels write every position of every call's slice; these two clear the rest of the arena, which
+  // this API copies back to the caller whole)
   if (e == hipSuccess) e = hipMemsetAsync(ctx->onpos.p, 0, sizeof(int32_t) * qbytes, s);
   if (e == hipSuccess) e = hipMemsetAsync(ctx->omap.p, 0xff, sizeof(int32_t) * qbytes, s);
   if (e != hipSuccess) {
@@ -3415,8 +3417,8 @@ extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem*
   if (e == hipSuccess) e = hipMemcpyAsync(ctx->qseq_uc.p, qseq_uc, qbytes, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(ctx->s2qseq.p, qseq, qbytes, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(ctx->s2probs.p, dp.data(), sizeof(DevStage2Problem) * n, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemsetAsync(ctx->onpos.p, 0, sizeof(int32_t) * qbytes, s);
-  if (e == hipSuccess) e = hipMemsetAsync(ctx->omap.p, 0xff, sizeof(int32_t) * qbytes, s);
+  // (onpos / omap are not cleared: the seeding writes every position of every call's slice first, and
+  // the chaining reads nothing outside the slices)
   if (e != hipSuccess) {
     oligo_plan_free(plan);
     return fail(ctx, GMAPDP_ENOMEM, "stage-2 buffers: %s", e);
@@ -4097,8 +4099,8 @@ static void stage2_plan_free(gmapdp_stage2_plan* p) {
 static int stage2_plan_launch(gmapdp_ctx* ctx, const gmapdp_stage2_plan* P, const char* d_qseq, const char* d_qseq_uc,
                               gmapdp_stage2_result* d_results, hipStream_t s, bool seed, int chain) {
   if (seed) {
-    if (hipMemsetAsync(P->d_npos, 0, sizeof(int32_t) * P->qbytes, s) != hipSuccess)
-      return fail(ctx, GMAPDP_ELAUNCH, "stage-2 plan: %s", hipGetLastError());
+    // (no clearing of d_npos / d_map: the seeding kernels write npositions 0 and the 8-mer of every query
+    // position of every call before anything reads them, and nothing reads outside the calls' slices)
     int rc = gmapdp_oligo_plan_run(ctx, P->oplan, d_qseq_uc, P->d_ores, P->d_npos, P->d_map, P->d_table, P->d_diag, s);
     if (rc) return rc;
   }

@@ -91,9 +91,11 @@ constexpr int kS2NoPositions = 0, kS2Coverage = 1, kS2Chained = 2, kS2Overflow =
 // s2a with the chrpos array), which is all that get_cells' scan and the sweep read of them.  So on a
 // 214-kb window s2a no longer initialises ~8 200 32-B records per call, nor does s2c's scan re-read them.
 // Calls small enough for the LDS link table (its loader reads every record) still get zeroed records.
+// 16 B, one store: the score lives only in the score array, the chrpos in the maps array, and the link is
+// the predecessor's hit index within the call (-1: none; off[] ascends, so the hit index gives back the
+// query position, s2_hit_pos / s2_hit_pos_wave).
 struct __attribute__((aligned(16))) S2Hit {
-  uint32_t map_;  // (unused: the chrpos lives in the maps array)
-  int consec, root, fpos, fhit, tracei, score, q;
+  int consec, root, tracei, pred;
 };
 struct S2Diag {  // struct Diag_T (diagdef.h)
   uint32_t diagonal;
@@ -215,7 +217,7 @@ __device__ __forceinline__ void fill_range(int lane, uint32_t* dst, int a, int b
   for (int q = a + lane; q <= b; q += 64) dst[q] = f(q);
 }
 
-struct S2Best {
+struct S2Best {  // pp: the predecessor's query position (-1: none), ph: its hit index within the call
   int consec, root, pp, ph, score, tracei;
 };
 // The link is wave-uniform by construction (every update comes from readlane/readfirstlane values);
@@ -257,8 +259,8 @@ static __shared__ int s2_head[64];  // s2_dloop_multi: the entry whose hits star
 __device__ __forceinline__ int s2_u(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ uint32_t s2_u(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
-struct S2HV {  // one hit's link state
-  uint32_t map;
+struct S2HV {  // one hit's link state; hit: its index within the call (off[q] + its index at q), here and in
+  uint32_t map;  // the ring, so a link to it is stored as it stands
   int score, consec, tracei, root, hit;
 };
 struct S2E {  // a processed query position: its active hits
@@ -268,7 +270,7 @@ struct S2E {  // a processed query position: its active hits
 struct S2W {
   S2Hit* hits;
   const uint32_t* maps;  // chrpos per hit
-  int* sc;               // score per hit (kept equal to hits[].score)
+  int* sc;               // score per hit (fwd_scores)
   const int* off;
   int* actn;       // per query position: number of active hits (firstactive != -1 <=> actn > 0)
   int* alist;      // active hits of q at alist[off[q] ...] (hit indices, ascending)
@@ -298,13 +300,13 @@ __device__ __forceinline__ S2HV s2_bcast(const S2HV& v, int j) {
 
 // an entry's hit outside the ring (rare): its own function so that the ring path's loads stay
 // ds_* instructions instead of being merged into flat loads through a selected pointer
-__device__ __attribute__((noinline)) S2HV s2_load_global(const S2Hit* hits, const uint32_t* maps, const int* alist,
-                                                        int offq, int k) {
+__device__ __attribute__((noinline)) S2HV s2_load_global(const S2Hit* hits, const uint32_t* maps, const int* sc,
+                                                        const int* alist, int offq, int k) {
   S2HV v;
-  const int h = alist[offq + k];
-  const S2Hit& x = hits[offq + h];
-  v.map = maps[offq + h];
-  v.score = x.score;
+  const int h = offq + alist[offq + k];
+  const S2Hit x = hits[h];
+  v.map = maps[h];
+  v.score = sc[h];
   v.consec = x.consec;
   v.tracei = x.tracei;
   v.root = x.root;
@@ -313,7 +315,7 @@ __device__ __attribute__((noinline)) S2HV s2_load_global(const S2Hit* hits, cons
 }
 
 __device__ __forceinline__ S2HV s2_load(const S2W& W, const S2E& e, int k) {
-  if (!e.inring) return s2_load_global(W.hits, W.maps, W.alist, e.offq, k);  // (callers fence first)
+  if (!e.inring) return s2_load_global(W.hits, W.maps, W.sc, W.alist, e.offq, k);  // (callers fence first)
   S2HV v;
   const int s = (e.start + k) & (kS2Ring - 1);
   v.map = s2_ring.map[s];
@@ -715,7 +717,7 @@ __device__ __forceinline__ int s2_dloop_multi(S2W& W, const S2Pref& pf, int np, 
     v.root = s2_ring.root[r];
     v.hit = s2_ring.hit[r];
   } else if (act) {
-    v = s2_load_global(W.hits, W.maps, W.alist, eoff, k);
+    v = s2_load_global(W.hits, W.maps, W.sc, W.alist, eoff, k);
   }
   const int eend = sl + ec;  // one past the entry's last lane
   const int a = __shfl(v.tracei, sl, 64);
@@ -878,16 +880,9 @@ __device__ __forceinline__ S2Best s2_one(S2W& W, int q, uint32_t position, int n
   return b;
 }
 
-__device__ __forceinline__ void s2_store_link(S2W& W, int q, int offq, int hit, const S2Best& b) {
+__device__ __forceinline__ void s2_store_link(S2W& W, int offq, int hit, const S2Best& b) {
   if (W.lane == 0) {
-    S2Hit& x = W.hits[offq + hit];
-    x.consec = b.consec;
-    x.root = b.root;
-    x.fpos = b.pp;
-    x.fhit = b.ph;
-    x.tracei = b.tracei;
-    x.score = b.score;
-    x.q = q;
+    W.hits[offq + hit] = S2Hit{b.consec, b.root, b.tracei, b.ph};  // (ph: -1 with pp)
     W.sc[offq + hit] = b.score;
   }
 }
@@ -898,13 +893,7 @@ __device__ __forceinline__ void s2_mult(S2W& W, int q, int offq, int low, int hi
   const int nhits = high - low;
   if (np == 0) {
     for (int i = W.lane; i < nhits; i += 64) {
-      S2Hit& x = W.hits[offq + low + i];
-      x.consec = kS2K;
-      x.root = (int)W.maps[offq + low + i];
-      x.fpos = x.fhit = -1;
-      x.tracei = W.tracectr + 1 + i;
-      x.score = kS2K;
-      x.q = q;
+      W.hits[offq + low + i] = S2Hit{kS2K, (int)W.maps[offq + low + i], W.tracectr + 1 + i, -1};
       W.sc[offq + low + i] = kS2K;
     }
     W.tracectr += nhits;
@@ -960,7 +949,7 @@ __device__ __forceinline__ void s2_mult(S2W& W, int q, int offq, int low, int hi
       b.tracei = ++W.tracectr;
       b.score = kS2K;
     }
-    s2_store_link(W, q, offq, low + i, b);
+    s2_store_link(W, offq, low + i, b);
   }
   wave_sync();
 }
@@ -968,23 +957,17 @@ __device__ __forceinline__ void s2_mult(S2W& W, int q, int offq, int low, int hi
 // the members of a run (s2_sweep): lane = query position cb + lane, members Mm; links, active lists and
 // ring slots (its own function: the sweep's register budget is full)
 struct S2Run {
-  int score, consec, tracei, root, hit, q, cb, pushed, np;
+  int score, consec, tracei, root, hit, q, pushed, np;
 };
+// hit: the member's index at its position (off: the position's first hit), prev: the previous member's
+// index within the call (the link of every member but the first, which links to L.hit)
 __device__ __forceinline__ void s2_run_write(S2Hit* hits, int* sc, int* alist, int lane, int off, int hit,
-                                             int prevhit, uint32_t map, int qq, S2Run L, uint64_t Mm) {
+                                             int prev, uint32_t map, int qq, S2Run L, uint64_t Mm) {
   if (!((Mm >> lane) & 1ull)) return;
   const uint64_t below = Mm & ((1ull << lane) - 1ull);
   const int r = __popcll(below);
-  const int pl = below ? 63 - __clzll((long long)below) : -1;  // the previous member's lane
   const int dq = qq - L.q;
-  S2Hit& x = hits[off + hit];
-  x.consec = L.consec + dq;
-  x.root = L.root;
-  x.fpos = pl >= 0 ? L.cb + pl : L.q;
-  x.fhit = pl >= 0 ? prevhit : L.hit;
-  x.tracei = L.tracei;
-  x.score = L.score + dq;
-  x.q = qq;
+  hits[off + hit] = S2Hit{L.consec + dq, L.root, L.tracei, below ? prev : L.hit};
   sc[off + hit] = L.score + dq;
   alist[off] = hit;
   const int sl = (L.pushed + r) & (kS2Ring - 1);
@@ -993,7 +976,7 @@ __device__ __forceinline__ void s2_run_write(S2Hit* hits, int* sc, int* alist, i
   s2_ring.consec[sl] = L.consec + dq;
   s2_ring.tracei[sl] = L.tracei;
   s2_ring.root[sl] = L.root;
-  s2_ring.hit[sl] = hit;
+  s2_ring.hit[sl] = off + hit;
   const int ms = (L.np + r) & (kS2Meta - 1);
   s2_ring.eq[ms] = qq;
   s2_ring.en[ms] = 1;
@@ -1016,13 +999,8 @@ __device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, con
   if (q <= qend) {  // the first position with hits: every hit starts a path
     const int n = npos(q), offq = W.off[q];
     for (int i = lane; i < n; i += 64) {
-      S2Hit& x = W.hits[offq + i];
-      x.fpos = x.fhit = -1;
-      x.consec = kS2K;
-      x.root = 0;  // (the CALLOC'ed value the reference leaves, stage2.c:3760-3770)
-      x.tracei = -1;
-      x.score = kS2K;
-      x.q = q;
+      // (root 0: the CALLOC'ed value the reference leaves, stage2.c:3760-3770)
+      W.hits[offq + i] = S2Hit{kS2K, 0, -1, -1};
       W.sc[offq + i] = kS2K;
     }
   }
@@ -1082,9 +1060,9 @@ __device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, con
         const int lscore = s2_u(s2_ring.score[ls]), ltr = s2_u(s2_ring.tracei[ls]), lroot = s2_u(s2_ring.root[ls]),
                   lhit = s2_u(s2_ring.hit[ls]);
         const uint64_t mb = Mm & ((1ull << lane) - 1ull);
-        const int prevhit = __shfl(m_low, mb ? 63 - __clzll((long long)mb) : 0, 64);
-        s2_run_write(W.hits, W.sc, W.alist, lane, m_off, m_low, prevhit, m_rmap, qq,
-                     {lscore, lcons, ltr, lroot, lhit, last.q, cb, W.pushed, np}, Mm);
+        const int prev = __shfl(m_off + m_low, mb ? 63 - __clzll((long long)mb) : 0, 64);
+        s2_run_write(W.hits, W.sc, W.alist, lane, m_off, m_low, prev, m_rmap, qq,
+                     {lscore, lcons, ltr, lroot, lhit, last.q, W.pushed, np}, Mm);
         if ((inrun >> lane) & 1ull) W.actn[qq] = (int)((Mm >> lane) & 1ull);
         const int cnt = __popcll(Mm);
         S2_TALLY(n_runs, 1);
@@ -1095,7 +1073,7 @@ __device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, con
         if (lsc >= grand_score) {  // consec >= ENOUGH_CONSECUTIVE > EXON_DEFN
           grand_score = lsc;
           grand_q = lq;
-          grand_hit = __builtin_amdgcn_readlane(m_low, ll);
+          grand_hit = __builtin_amdgcn_readlane(m_off + m_low, ll);
           grand_map = (uint32_t)__builtin_amdgcn_readlane((int)m_rmap, ll);
         }
         const int loff = __builtin_amdgcn_readlane(m_off, ll);
@@ -1163,10 +1141,10 @@ __device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, con
       if (have_best && best_score >= grand_score && b.consec > kS2ExonDefn) {
         grand_score = best_score;
         grand_q = q;
-        grand_hit = low;
+        grand_hit = qoff + low;
         grand_map = position;
       }
-      s2_store_link(W, q, qoff, low, b);
+      s2_store_link(W, qoff, low, b);
       const int threshold = max(b.score - kS2ScoreRestrict, 0);
       if (b.score > threshold) {
         nact = 1;
@@ -1178,7 +1156,7 @@ __device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, con
           s2_ring.consec[sl] = b.consec;
           s2_ring.tracei[sl] = b.tracei;
           s2_ring.root[sl] = b.root;
-          s2_ring.hit[sl] = low;
+          s2_ring.hit[sl] = qoff + low;
         }
       }
     } else if (high - low > 1 && high - low <= 64) {
@@ -1362,18 +1340,11 @@ __device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, con
       if (best_hit >= 0 && best_score >= grand_score && __builtin_amdgcn_readlane(mb.consec, bl) > kS2ExonDefn) {
         grand_score = best_score;
         grand_q = q;
-        grand_hit = best_hit;
+        grand_hit = qoff + best_hit;
         grand_map = (uint32_t)__builtin_amdgcn_readlane((int)cm, bl);
       }
       if (lane < nh) {
-        S2Hit& x = W.hits[qoff + low + lane];
-        x.consec = mb.consec;
-        x.root = mb.root;
-        x.fpos = mb.pp;
-        x.fhit = mb.ph;
-        x.tracei = mb.tracei;
-        x.score = mb.score;
-        x.q = q;
+        W.hits[qoff + low + lane] = S2Hit{mb.consec, mb.root, mb.tracei, mb.ph};
         W.sc[qoff + low + lane] = mb.score;
       }
       // revise_active_lookback + the entry's active hits into the ring
@@ -1389,7 +1360,7 @@ __device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, con
         s2_ring.consec[sl] = mb.consec;
         s2_ring.tracei[sl] = mb.tracei;
         s2_ring.root[sl] = mb.root;
-        s2_ring.hit[sl] = low + lane;
+        s2_ring.hit[sl] = qoff + low + lane;
       }
       nact = __popcll(am);
     } else {
@@ -1412,7 +1383,7 @@ __device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, con
         best_score = bs;
         best_hit = bh;
         if (bh >= 0) {
-          best_fhit = W.hits[qoff + bh].fhit;
+          best_fhit = W.hits[qoff + bh].pred;
           best_consec = W.hits[qoff + bh].consec;
         }
         nskipped = 0;
@@ -1426,10 +1397,8 @@ __device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, con
               if (xmap > grand_map + W.maxintronlen) continue;
               if (xmap >= grand_map + (uint32_t)kS2K) {
                 x.consec = kS2K;
-                x.fpos = grand_q;
-                x.fhit = grand_hit;
+                x.pred = grand_hit;
                 x.tracei = W.tracectr + 1 + (i - low);  // fresh per relinked hit
-                x.score = best_score;
                 W.sc[qoff + i] = best_score;
               }
             }
@@ -1441,7 +1410,7 @@ __device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, con
         if (best_hit >= 0 && best_score >= grand_score && best_consec > kS2ExonDefn) {
           grand_score = best_score;
           grand_q = q;
-          grand_hit = best_hit;
+          grand_hit = qoff + best_hit;
           grand_map = W.maps[qoff + best_hit];
         }
         // revise_active_lookback + the entry's active hits into the ring
@@ -1455,11 +1424,13 @@ __device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, con
           const int i = c0 + lane;
           S2Hit x = {};
           uint32_t xmap = 0;
+          int xscore = 0;
           bool a = false;
           if (i < high) {
             x = W.hits[qoff + i];
             xmap = W.maps[qoff + i];
-            a = x.score > threshold;
+            xscore = W.sc[qoff + i];
+            a = xscore > threshold;
           }
           const uint64_t m = ballot(a);
           if (a) {
@@ -1468,11 +1439,11 @@ __device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, con
             if (high - low <= kS2Ring) {
               const int sl = (W.pushed + r) & (kS2Ring - 1);
               s2_ring.map[sl] = xmap;
-              s2_ring.score[sl] = x.score;
+              s2_ring.score[sl] = xscore;
               s2_ring.consec[sl] = x.consec;
               s2_ring.tracei[sl] = x.tracei;
               s2_ring.root[sl] = x.root;
-              s2_ring.hit[sl] = i;
+              s2_ring.hit[sl] = qoff + i;
             }
           }
           nact += __popcll(m);
@@ -1535,16 +1506,42 @@ __device__ __forceinline__ char s2_genomic_nt(const uint32_t* __restrict__ block
 
 // traceback_one (stage2.c:4140): drop the 3'-end links with fewer than MIN_TERMINAL_NCONSECUTIVE
 // consecutive matches, then visit the path's hits 3' end first (Pairpool_push drops chrpos >= 2^31)
-template <class F>
-__device__ void s2_walk(const S2Hit* hits, const uint32_t* maps, const int* off, int gi, F visit) {
-  while (gi >= 0 && hits[gi].consec < kS2MinTerminal) {
-    const int fq = hits[gi].fpos;
-    gi = fq >= 0 ? off[fq] + hits[gi].fhit : -1;
+// The query position of hit h (its index within the call): the last q with off[q] <= h.  off[0 .. ql]
+// ascends from 0 to the hit count, and a position without hits shares its successor's offset, so that q
+// is the one position whose hits include h.  One lane: a binary search.
+__device__ __forceinline__ int s2_hit_pos(const int* __restrict__ off, int ql, int h) {
+  int lo = 0, hi = ql;  // off[lo] <= h < off[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (off[mid] <= h) lo = mid;
+    else hi = mid;
   }
+  return lo;
+}
+// The same for a wave-uniform h by the whole wave: 64 probes per round trip (two for a 2-kb query)
+__device__ __forceinline__ int s2_hit_pos_wave(const int* __restrict__ off, int ql, int h, int lane) {
+  int lo = 0, hi = ql;  // off[lo] <= h < off[hi]
+  while (hi - lo > 1) {
+    const int step = (hi - lo + 63) >> 6;
+    const int p = lo + lane * step;  // lane 0 probes lo itself: true
+    const uint64_t m = ballot(p < hi && off[p] <= h);  // a prefix of the lanes
+    lo += (63 - __clzll((long long)m)) * step;
+    hi = min(hi, lo + step);
+  }
+  return lo;
+}
+
+template <class F>
+__device__ void s2_walk(const S2Hit* hits, const uint32_t* maps, const int* off, int ql, int gi, F visit) {
+  while (gi >= 0 && hits[gi].consec < kS2MinTerminal) gi = hits[gi].pred;
+  if (gi < 0) return;
+  int q = s2_hit_pos(off, ql, gi);
   while (gi >= 0) {
-    if ((int)maps[gi] >= 0) visit(gi);
-    const int fq = hits[gi].fpos;
-    gi = fq >= 0 ? off[fq] + hits[gi].fhit : -1;
+    if ((int)maps[gi] >= 0) visit(gi, q);
+    gi = hits[gi].pred;
+    if (gi >= 0)  // a link goes to an earlier position: step down to the one holding gi
+      while (q > 0 && off[--q] > gi) {
+      }
   }
 }
 
@@ -1982,13 +1979,7 @@ __global__ __launch_bounds__(64) void s2a_kernel(
       if (h < hend) {
         map = table_all[O.table_offset + mj + (h - oq)];  // (mappings relative to the call's table)
         big |= (map >= 0x80000000u);
-        if (records) {
-          S2Hit x;
-          x.map_ = map;
-          x.consec = x.root = x.fpos = x.fhit = x.tracei = x.score = 0;  // CALLOC
-          x.q = cb + j;
-          hits[h] = x;
-        }
+        if (records) hits[h] = S2Hit{0, 0, 0, 0};  // CALLOC (a zero link: position 0's hit 0)
         mapsa[h] = map;
         sca[h] = 0;
       }
@@ -2136,45 +2127,52 @@ struct S2WalkOut {
 // indices and s2_walk_wave would advance one node per step).  A path mostly follows one diagonal through
 // consecutive query positions, so each step guesses the next 64 nodes there: lane k takes the hit of
 // position q - k with map - k (a binary search in that position's hits, which ascend), and the guesses
-// hold while each one is its predecessor's link (fpos, fhit); the walk goes on from the last holding
-// node's real link.  Same nodes, order and outputs as s2_walk.
-__device__ S2WalkOut s2_walk_diag(const S2Hit* hits, const uint32_t* maps, const int* scs, const int* off, int gi,
-                                  int lane, int* pq, int* ph) {
+// hold while each one is its predecessor's link; the walk goes on from the last holding node's real link.
+// A node's query position is not stored: the guesses know theirs, and after a real link it is first
+// taken to continue the run (the position before the last node's, checked against off[] by the loads the
+// guesses make anyway), else found by one wave search of off[].  Same nodes, order and outputs as s2_walk.
+__device__ S2WalkOut s2_walk_diag(const S2Hit* __restrict__ hits, const uint32_t* __restrict__ maps,
+                                  const int* __restrict__ scs, const int* __restrict__ off, int ql, int gi, int lane,
+                                  int* __restrict__ pq, int* __restrict__ ph) {
   S2WalkOut o = {0, -1, -1};
-  while (gi >= 0 && hits[gi].consec < kS2MinTerminal) {  // prune the 3' end
-    const int fq = hits[gi].fpos;
-    gi = fq >= 0 ? off[fq] + hits[gi].fhit : -1;
-  }
+  while (gi >= 0 && hits[gi].consec < kS2MinTerminal) gi = hits[gi].pred;  // prune the 3' end
+  int qn = -1;  // gi's query position (-1: not known)
   while (gi >= 0) {
-    const int qn = s2_u(hits[gi].q);
+    if (qn < 0) qn = s2_hit_pos_wave(off, ql, gi, lane);
+    int p = qn - lane;
+    int lo = p >= 0 ? off[p] : 0, hi = p >= 0 ? off[p + 1] : 0;
+    if (!(s2_u(lo) <= gi && gi < s2_u(hi))) {  // the link left the run of positions
+      qn = s2_hit_pos_wave(off, ql, gi, lane);
+      p = qn - lane;
+      lo = p >= 0 ? off[p] : 0;
+      hi = p >= 0 ? off[p + 1] : 0;
+    }
     const uint32_t mn = s2_u(maps[gi]);
-    const int p = qn - lane;
+    const uint32_t target = mn - (uint32_t)lane;
     int idx = -1;
     if (lane == 0) {
       idx = gi;
     } else if (p >= 0) {
-      const uint32_t target = mn - (uint32_t)lane;
-      int lo = off[p], hi = off[p + 1];
       const int end = hi;
-      while (lo < hi) {  // (4 B per hit: a step's 64 searches touch ~1 KB, not the 36-B records' ~9 KB)
+      while (lo < hi) {  // (4 B per hit: a step's 64 searches touch ~1 KB, not the records' ~4 KB)
         const int mid = (lo + hi) >> 1;
         if (maps[mid] < target) lo = mid + 1;
         else hi = mid;
       }
       if (lo < end && maps[lo] == target) idx = lo;
     }
-    int pred = -1;
-    uint32_t mx = 0x80000000u;
-    int qx = 0;
     // a guess the sweep never scored (score 0) is on no path, and its record was never written: it fails
     // (a path node's link always points at a scored hit, so such a guess could not hold anyway)
-    if (idx >= 0 && lane > 0 && scs[idx] <= 0) idx = -1;
-    if (idx >= 0) {
-      const S2Hit& x = hits[idx];
-      pred = x.fpos >= 0 ? off[x.fpos] + x.fhit : -1;
-      mx = maps[idx];
-      qx = x.q;
+    int sc = 0;
+    S2Hit x = {0, 0, 0, -1};
+    if (idx >= 0) {  // (both loads issued together; an unwritten record is read and dropped)
+      sc = scs[idx];
+      x = hits[idx];
     }
+    if (lane > 0 && sc <= 0) idx = -1;
+    const int pred = idx >= 0 ? x.pred : -1;
+    const uint32_t mx = idx >= 0 ? target : 0x80000000u;  // (the node's chrpos: mn, or the guess it matched)
+    const int qx = p;
     // node k holds when node k - 1 does and node k - 1's link is this guess
     const int prev_pred = __shfl_up(pred, 1, 64);
     const bool c = lane == 0 || (idx >= 0 && prev_pred == idx);
@@ -2194,6 +2192,7 @@ __device__ S2WalkOut s2_walk_diag(const S2Hit* hits, const uint32_t* maps, const
     }
     o.n += __popcll(vm);
     gi = __builtin_amdgcn_readlane(pred, len - 1);
+    qn = max(qn - len, -1);  // the position a continuing run would have (checked above)
   }
   return o;
 }
@@ -2288,18 +2287,41 @@ __global__ __launch_bounds__(64) void s2c_kernel(
   // one pass over the scores: the hits within the tolerance of the running best (a superset of those
   // within it of the final best, in hit order) with their scores, then the final best filters them
   const int h0 = off[qstart], h1 = off[qend + 1];
+  // Per candidate slot: cand its hit, keep its score, cq its query position, croot its root, so the sorts
+  // below compare slots with one load per key.  The path records' room (written from the walks on) holds
+  // the last two and the two slot lists.
+  const int H = T > 0 ? T : 1;
+  int* cq = reinterpret_cast<int*>(pth);
+  int* croot = cq + H;
+  int* slots = croot + H;
+  int* sorted = slots + H;
   int best = 0, ncand = 0;
-  for (int cb = h0; cb < h1; cb += 64) {
-    const int gi = cb + lane;
-    const int sc = gi < h1 ? scs[gi] : 0;  // (the compact score array: unscored hits hold 0)
-    best = max(best, wave_max_i(sc));
-    const bool c = gi < h1 && sc > best - kS2FinalTolerance && sc > 0;
-    const uint64_t m = ballot(c);
-    if (c) {
-      cand[ncand + lanes_below(m, lane)] = gi;
-      keep[ncand + lanes_below(m, lane)] = sc;
+  {
+    // eight 64-hit chunks of the scores per step, loaded before any use: one round trip per 512 hits
+    const int* __restrict__ scr = scs;
+    int* __restrict__ cw = cand;
+    int* __restrict__ kw = keep;
+    constexpr int kB = 8;
+    for (int cb = h0; cb < h1; cb += 64 * kB) {
+      int sc[kB];
+#pragma unroll
+      for (int k = 0; k < kB; k++) {
+        const int gi = cb + 64 * k + lane;
+        sc[k] = gi < h1 ? scr[gi] : 0;  // (the compact score array: unscored hits hold 0)
+      }
+#pragma unroll
+      for (int k = 0; k < kB; k++) {
+        const int gi = cb + 64 * k + lane;
+        best = max(best, wave_max_i(sc[k]));
+        const bool c = gi < h1 && sc[k] > best - kS2FinalTolerance && sc[k] > 0;
+        const uint64_t m = ballot(c);
+        if (c) {
+          cw[ncand + lanes_below(m, lane)] = gi;
+          kw[ncand + lanes_below(m, lane)] = sc[k];
+        }
+        ncand += __popcll(m);
+      }
     }
-    ncand += __popcll(m);
   }
   wave_sync();
   if (best > 0) {
@@ -2309,7 +2331,14 @@ __global__ __launch_bounds__(64) void s2c_kernel(
       const int gi = i < ncand ? cand[i] : 0, sc = i < ncand ? keep[i] : 0;
       const bool c = i < ncand && sc > best - kS2FinalTolerance;
       const uint64_t m = ballot(c);
-      if (c) cand[n2 + lanes_below(m, lane)] = gi;  // in place: n2 <= cb, this chunk's loads came first
+      if (c) {  // in place: n2 <= cb, this chunk's loads came first
+        const int s = n2 + lanes_below(m, lane);
+        cand[s] = gi;
+        keep[s] = sc;
+        cq[s] = s2_hit_pos(off, ql, gi);
+        croot[s] = hits[gi].root;
+        slots[s] = s;
+      }
       n2 += __popcll(m);
     }
     ncand = n2;
@@ -2319,20 +2348,19 @@ __global__ __launch_bounds__(64) void s2c_kernel(
   wave_sync();
   // get_cells_fwd: by (root asc, score desc, querypos desc, hit asc); each root's best cells are the
   // first of its group and those with the same score
-  wave_sort(lane, ncand, cand, keep, sbuf, [&](int a, int b) {
-    const S2Hit &x = hits[a], &y = hits[b];
-    if (x.root != y.root) return x.root < y.root;
-    if (x.score != y.score) return x.score > y.score;
-    if (x.q != y.q) return x.q > y.q;
-    return a < b;
+  wave_sort(lane, ncand, slots, sorted, sbuf, [&](int a, int b) {
+    if (croot[a] != croot[b]) return croot[a] < croot[b];
+    if (keep[a] != keep[b]) return keep[a] > keep[b];
+    if (cq[a] != cq[b]) return cq[a] > cq[b];
+    return cand[a] < cand[b];
   });
   int nkeep = 0, gcarry = 0;
   for (int cb = 0; cb < ncand; cb += 64) {
     const int i = cb + lane;
-    int gi = -1, gstart = 0;
+    int s = 0, gstart = 0;
     if (i < ncand) {
-      gi = keep[i];
-      gstart = (i == 0 || hits[keep[i - 1]].root != hits[gi].root) ? i : 0;
+      s = sorted[i];
+      gstart = (i == 0 || croot[sorted[i - 1]] != croot[s]) ? i : 0;
     }
     int m = gstart;  // the group's first element: running maximum of the group starts
 #pragma unroll
@@ -2342,24 +2370,25 @@ __global__ __launch_bounds__(64) void s2c_kernel(
     }
     m = max(m, gcarry);
     gcarry = __shfl(m, 63, 64);
-    const bool k = i < ncand && hits[gi].score == hits[keep[m]].score;
+    const bool k = i < ncand && keep[s] == keep[sorted[m]];
     const uint64_t bm = ballot(k);
-    if (k) cand[nkeep + lanes_below(bm, lane)] = gi;
+    if (k) slots[nkeep + lanes_below(bm, lane)] = s;  // (slots is read no more)
     nkeep += __popcll(bm);
   }
   wave_sync();
   // Cell_score_cmp, stable over that order: (score desc, root asc, querypos desc, hit asc)
-  wave_sort(lane, nkeep, cand, keep, sbuf, [&](int a, int b) {
-    const S2Hit &x = hits[a], &y = hits[b];
-    if (x.score != y.score) return x.score > y.score;
-    if (x.root != y.root) return x.root < y.root;
-    if (x.q != y.q) return x.q > y.q;
-    return a < b;
+  wave_sort(lane, nkeep, slots, sorted, sbuf, [&](int a, int b) {
+    if (keep[a] != keep[b]) return keep[a] > keep[b];
+    if (croot[a] != croot[b]) return croot[a] < croot[b];
+    if (cq[a] != cq[b]) return cq[a] > cq[b];
+    return cand[a] < cand[b];
   });
-  for (int i = lane; i < nkeep; i += 64) cand[i] = keep[i];
+  for (int i = lane; i < nkeep; i += 64) slots[i] = cand[sorted[i]];
+  wave_sync();
+  for (int i = lane; i < nkeep; i += 64) cand[i] = slots[i];
   wave_sync();
   int npaths = 0;
-  while (npaths < nkeep && (npaths < kS2MaxNalignments || hits[cand[npaths]].score == best)) npaths++;
+  while (npaths < nkeep && (npaths < kS2MaxNalignments || scs[cand[npaths]] == best)) npaths++;
   R.npaths = npaths;
 
   S2_MARK(5);
@@ -2371,33 +2400,27 @@ __global__ __launch_bounds__(64) void s2c_kernel(
   uint32_t* lmap = s2c_lds + kS2cCap;
   const bool lds_walk = kLdsWalk;  // T <= kS2cCap && nq <= 65536 (checked above): 15-bit hit index, 16-bit querypos
   if (lds_walk && npaths > 0) {
-    // four hits per lane per step: their loads, then their off[] gathers, overlap
-    for (int b0 = lane; b0 < T; b0 += 256) {
-      int fp[4], fh[4], cs[4], qq[4];
-      uint32_t mp[4];
+    // 64 query positions per step (lane j holds off[cb + j]), their hits 64 at a time: a hit's position is
+    // the last lane whose offset is <= the hit, a binary search over the lanes as in s2a_kernel's layout
+    const S2Hit* __restrict__ hr = hits;
+    const uint32_t* __restrict__ mr = maps;
+    const int* __restrict__ offr = off;
+    for (int cb = 0; cb < ql; cb += 64) {
+      const int o = offr[min(cb + lane, ql)];
+      const int hbeg = __shfl(o, 0, 64), hend = s2_u(offr[min(cb + 64, ql)]);
+      for (int base = hbeg; base < hend; base += 64) {
+        const int h = base + lane;
+        int j = 0;
 #pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int i = b0 + 64 * k;
-        fp[k] = -1;
-        if (i < T) {
-          const S2Hit& x = hits[i];
-          fp[k] = x.fpos;
-          fh[k] = x.fhit;
-          cs[k] = x.consec;
-          mp[k] = maps[i];
-          qq[k] = x.q;
+        for (int st = 32; st >= 1; st >>= 1) {
+          const int oj = __shfl(o, j + st, 64);
+          if (oj <= h) j += st;
         }
-      }
-      int ob[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) ob[k] = fp[k] >= 0 ? off[fp[k]] : 0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int i = b0 + 64 * k;
-        if (i < T) {
-          const uint32_t pr = fp[k] >= 0 ? (uint32_t)(ob[k] + fh[k]) : kS2NoPred;
-          llq[i] = ((uint32_t)qq[k] << 16) | (cs[k] < kS2MinTerminal ? 0x8000u : 0u) | pr;
-          lmap[i] = mp[k];
+        if (h < hend) {
+          const S2Hit x = hr[h];
+          const uint32_t pr = x.pred >= 0 ? (uint32_t)x.pred : kS2NoPred;
+          llq[h] = ((uint32_t)(cb + j) << 16) | (x.consec < kS2MinTerminal ? 0x8000u : 0u) | pr;
+          lmap[h] = mr[h];
         }
       }
     }
@@ -2417,16 +2440,16 @@ __global__ __launch_bounds__(64) void s2c_kernel(
     int n = 0, top = -1, bottom = -1;
     if (lds_walk || nq <= 65536) {
       const S2WalkOut o = lds_walk ? s2_walk_wave(llq, lmap, cell, lane, single ? pathq : nullptr, pathh)
-                                   : s2_walk_diag(hits, maps, scs, off, cell, lane, single ? pathq : nullptr, pathh);
+                                   : s2_walk_diag(hits, maps, scs, off, ql, cell, lane, single ? pathq : nullptr, pathh);
       n = o.n;
       top = o.top;
       bottom = o.bottom;
     } else if (lane == 0) {
-      s2_walk(hits, maps, off, cell, [&](int gi) {
+      s2_walk(hits, maps, off, ql, cell, [&](int gi, int q) {
         if (n == 0) top = gi;
         bottom = gi;
         if (single) {
-          pathq[n] = hits[gi].q;
+          pathq[n] = q;
           pathh[n] = (int)maps[gi];
         }
         n++;
@@ -2499,12 +2522,12 @@ __global__ __launch_bounds__(64) void s2c_kernel(
     const int n = x.n;
     if (!single && (lds_walk || nq <= 65536)) {  // entries, 3' end first
       if (lds_walk) (void)s2_walk_wave(llq, lmap, x.cell, lane, pathq, pathh);
-      else (void)s2_walk_diag(hits, maps, scs, off, x.cell, lane, pathq, pathh);
+      else (void)s2_walk_diag(hits, maps, scs, off, ql, x.cell, lane, pathq, pathh);
     } else if (lane == 0 && !single) {
       int e = 0;
       {
-        s2_walk(hits, maps, off, x.cell, [&](int gi) {
-          pathq[e] = hits[gi].q;
+        s2_walk(hits, maps, off, ql, x.cell, [&](int gi, int q) {
+          pathq[e] = q;
           pathh[e] = (int)maps[gi];
           e++;
         });

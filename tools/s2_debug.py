@@ -30,7 +30,7 @@ def layout(ql, T, nd):
     s["ord"] = a16(s["diags"] + 32 * D)
     s["tmp"] = a16(s["ord"] + 4 * D)
     s["hits"] = a16(s["tmp"] + 4 * D)
-    s["maps"] = a16(s["hits"] + 32 * H)  # S2Hit {map_ (unused), consec, root, fpos, fhit, tracei, score, q}
+    s["maps"] = a16(s["hits"] + 16 * H)  # S2Hit {consec, root, tracei, pred}
     s["sc"] = a16(s["maps"] + 4 * H)
     s["end"] = a16(s["sc"] + 4 * H)
     return s
@@ -59,16 +59,26 @@ def main(k=0):
     eng.lib.gmapdp_debug_stage2_scratch(eng.h, raw.ctypes.data, C.c_size_t(L["end"]))
     minact = raw[L["minact"]:L["minact"] + 4 * ql].view(np.uint32).astype(np.int64)
     maxact = raw[L["maxact"]:L["maxact"] + 4 * ql].view(np.uint32).astype(np.int64)
-    rec = raw[L["hits"]:L["hits"] + 32 * T].view(np.int32).reshape(T, 8)
+    rec = raw[L["hits"]:L["hits"] + 16 * T].view(np.int32).reshape(T, 4)
+    off = raw[L["off"]:L["off"] + 4 * (ql + 1)].view(np.int32)
     maps = raw[L["maps"]:L["maps"] + 4 * T].view(np.int32)
     scs = raw[L["sc"]:L["sc"] + 4 * T].view(np.int32)
     # the oracle's field order {map, consec, root, fpos, fhit, tracei, score, active} (+ q): records are
-    # written only for the hits the sweep scores, so compare those (score > 0)
+    # written only for the hits the sweep scores, so compare those (score > 0).  The record's link is the
+    # predecessor's hit index; its (fpos, fhit) and a hit's own q come back from off[] (the last position
+    # whose offset is <= the index).
+    def pos_of(h):
+        return np.searchsorted(off, h, side="right") - 1
+    pred = rec[:, 3]
+    fpos = np.where(pred >= 0, pos_of(np.maximum(pred, 0)), -1)
     hits = np.zeros((T, 9), dtype=np.int32)
     hits[:, 0] = maps
-    hits[:, 1:7] = rec[:, 1:7]
+    hits[:, 1:3] = rec[:, 0:2]
+    hits[:, 3] = fpos
+    hits[:, 4] = np.where(pred >= 0, pred - off[np.maximum(fpos, 0)], -1)
+    hits[:, 5] = rec[:, 2]
     hits[:, 6] = scs
-    hits[:, 8] = rec[:, 7]
+    hits[:, 8] = pos_of(np.arange(T))
     print("problem", k, "T", T, "nd", nd, "ql", ql, "equal results:", got == o, "exp==orc:", exp[k] == o)
     omin = ob[:ql].view(np.uint32).astype(np.int64)
     omax = ob[ql:2 * ql].view(np.uint32).astype(np.int64)
