@@ -18,8 +18,9 @@
 //
 // Design.  One wave per Stage2_compute call.  The wave does the data-parallel parts: coverage and
 // diagonal depth (difference arrays + wave prefix scans), the minactive / maxactive lines (a segment
-// list, each segment filled by all lanes), the per-hit arrays (the hits of every query position laid
-// out contiguously by a prefix scan of npositions, so a link is one index), the cell selection (a
+// list, each segment filled by all lanes), the per-hit arrays (of every query position the hits inside
+// [minactive, maxactive], laid out contiguously by a prefix scan of their counts, so a link is one index;
+// the first position with hits keeps all of them: s2a_kernel), the cell selection (a
 // max-reduction, a compaction of the cells within FINAL_SCORE_TOLERANCE of the best, group maxima and
 // ranks by lane), the duplicate filter and convert_to_nucleotides (per path entry record counts, a
 // prefix scan, every record written in place in list order).  The querypos sweep of
@@ -49,6 +50,15 @@ constexpr int kS2MaxNalignments = 10;   // gmap.c:142
 constexpr int kS2Sufflookback = 60, kS2Nsufflookback = 5;  // gmap.c:269-270
 constexpr int kS2ExtraBounds = 20;      // diag.c:14
 constexpr int kS2cCap = 4096;           // hits of s2c's LDS link table (8 B each, 32 KB: 5 waves per CU)
+// Which of s2c's two launches takes a call: the one with the LDS link table when it holds the call's hits
+// and a query position fits 16 bits.  seeded: the seeding's hit count, laid: the hits s2a laid out (<= seeded).
+// s2a (zeroed records or not) and both s2c launches evaluate this alike.
+#ifndef GMAPDP_S2C_CLASS_LAID
+#define GMAPDP_S2C_CLASS_LAID 0  // 1: by the laid-out count (variants: make variant DEFS=...)
+#endif
+__host__ __device__ inline bool s2c_lds_class(int seeded, int laid, int nq) {
+  return (GMAPDP_S2C_CLASS_LAID ? laid : seeded) <= kS2cCap && nq <= 65536;
+}
 
 // Phase timing (tools/oi_timing.py s2; the GMAPDP_OI_TIMING variant of the library only)
 #ifdef GMAPDP_OI_TIMING
@@ -88,9 +98,9 @@ constexpr int kS2NoPositions = 0, kS2Coverage = 1, kS2Chained = 2, kS2Overflow =
 
 // struct Link_T (stage2.c:363) + fwd_scores, one per (querypos, hit).  Written by the sweep (s2b) for every
 // hit it scores; the hits it never scores keep score 0 in the compact score array (4 B per hit, zeroed by
-// s2a with the chrpos array), which is all that get_cells' scan and the sweep read of them.  So on a
-// 214-kb window s2a no longer initialises ~8 200 32-B records per call, nor does s2c's scan re-read them.
-// Calls small enough for the LDS link table (its loader reads every record) still get zeroed records.
+// s2a with the chrpos array), which is all that get_cells' scan and the sweep read of them.  Only the hits
+// the chaining can touch are laid out at all (s2a_kernel: about 1 900 of the ~8 200 a 214-kb window seeds
+// per call).  Calls of the LDS link table's class (its loader reads every record) get zeroed records.
 // 16 B, one store: the score lives only in the score array, the chrpos in the maps array, and the link is
 // the predecessor's hit index within the call (-1: none; off[] ascends, so the hit index gives back the
 // query position, s2_hit_pos / s2_hit_pos_wave).
@@ -138,7 +148,7 @@ __host__ __device__ inline S2Scratch s2_scratch(int ql, int T, int nd) {
   s.paths = align16(s.keep + 4 * H);
   s.pq = align16(s.paths + sizeof(S2Path) * H);
   s.ph = align16(s.pq + 4 * Q);
-  s.lh = align16(s.ph + 4 * Q);  // the sweep's active range per position: low[Q], high[Q] (s2a_kernel)
+  s.lh = align16(s.ph + 4 * Q);  // the active range [low, high) of the first position with hits (s2a_kernel)
   s.sortn = s2_pow2((int)(H > D ? H : D));
   s.sbuf = align16(s.lh + 8 * Q);
   s.total = align16(s.sbuf + 4 * (size_t)s.sortn);
@@ -985,8 +995,8 @@ __device__ __forceinline__ void s2_run_write(S2Hit* hits, int* sc, int* alist, i
 }
 
 // the sweep (stage2.c:3746-4080)
-__device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, const int* lowa, const int* higha,
-                                         const uint32_t* rmapa, int qstart, int qend) {
+__device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, const int* fp, const uint32_t* rmapa,
+                                         int qstart, int qend) {
   const int lane = W.lane;
   auto npos = [&](int q) { return q < nq ? npq[q] : 0; };
   int q = 0, np = 0;
@@ -996,8 +1006,14 @@ __device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, con
     if (lane == 0) W.actn[q] = 0;
     q++;
   }
+  // The first position with hits keeps every hit in the layout, its active range [low0, high0) beside it;
+  // any other position's laid-out hits are its active range (s2a_kernel)
+  const int q0 = q;
+  int low0 = 0, high0 = 0;
   if (q <= qend) {  // the first position with hits: every hit starts a path
     const int n = npos(q), offq = W.off[q];
+    low0 = s2_u(fp[0]);
+    high0 = s2_u(fp[1]);
     for (int i = lane; i < n; i += 64) {
       // (root 0: the CALLOC'ed value the reference leaves, stage2.c:3760-3770)
       W.hits[offq + i] = S2Hit{kS2K, 0, -1, -1};
@@ -1010,7 +1026,7 @@ __device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, con
   uint32_t grand_map = 0;
   S2E last = {0, 0, 0, 0, false};
   // per-position metadata for the chunk [cb, cb + 64): npositions, off, and the hits inside [minactive,
-  // maxactive]: [m_low, m_high), m_rmap the first of them (s2a_kernel's binary searches)
+  // maxactive]: [m_low, m_high) = [0, off[q + 1] - off[q]) but at q0, m_rmap the first of them (s2a_kernel)
   int cb = -1, m_n = 0, m_off = 0, m_low = 0, m_high = 0;
   uint32_t m_rmap = 0;
 #ifdef GMAPDP_OI_TIMING
@@ -1031,8 +1047,9 @@ __device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, con
       const bool in = qq <= qend;
       m_n = qq < nq ? npq[qq] : 0;
       m_off = qq <= qend + 1 ? W.off[qq] : 0;
-      m_low = in ? lowa[qq] : 0;
-      m_high = in ? higha[qq] : 0;
+      const int o1 = in ? W.off[qq + 1] : 0;  // (qend < querylength: off[qend + 1] exists)
+      m_low = qq == q0 ? low0 : 0;
+      m_high = qq == q0 ? high0 : o1 - m_off;
       m_rmap = in ? rmapa[qq] : 0u;
     }
     const int j = q - cb;
@@ -1928,40 +1945,100 @@ __global__ __launch_bounds__(64) void s2a_kernel(
 
   S2_MARK(2);
   // ---- per-hit arrays: the hits of query position q at hits[off[q] ...] (Linkmatrix_1d_new) ----
-  // 64 positions at a time: their offsets by a prefix scan, then their hits written in hit order, lane l
-  // taking hit base + l (its position the last lane whose offset is <= the hit, a binary search over the
-  // lanes), so each store instruction covers 64 consecutive records
+  // Only the hits the chaining can touch are laid out.  The sweep scores the hits of q inside [minactive,
+  // maxactive] (stage2.c:3849-3857); a position's hits ascend in chrpos, so they are [low, high): low the
+  // first hit with map >= minactive, high the first with map > max(maxactive, minactive - 1) (the search
+  // from low: an empty range when maxactive < minactive).  revise_active_lookback (:4070) rebuilds the
+  // active list from that range alone before any later position looks back, so a hit outside it is never a
+  // lookback target, and its fwd_score stays 0: never a cell (get_cells_fwd :3450), never on a path.  The
+  // one exception is q0, the first position with hits at or after querystart: the reference gives every
+  // hit of it fwd_score = indexsize (:3792-3815), so the ones outside the range are cells of score 8, which
+  // reach the paths of a call whose best score is below 8 + FINAL_SCORE_TOLERANCE.  q0 therefore keeps all
+  // its hits, and its range goes to the sweep beside the arrays (fp[0], fp[1]); every other position's
+  // range is its whole compact slice.
   //
-  // The same pass gives the sweep its active range per query position (stage2.c:1104-1110, 1488-1494):
-  // the hits of q inside [minactive, maxactive] are [low, high), rmap the first of them.  A position's hits
-  // ascend in chrpos, so low is the first hit with map >= minactive and high the first with
-  // map > max(maxactive, minactive - 1) (the search from low: an empty range when maxactive < minactive),
-  // each written by the one hit lane where the predicate turns true, or by the position's last hit (n)
-  // when it never does.  The sweep's chunk metadata is then one round of independent loads.
-  int* lowa = reinterpret_cast<int*>(S + so.lh);
-  int* higha = lowa + (ql + 1);
+  // 64 positions at a time, each lane its position's range in its table slice (one round of loads for a
+  // slice of <= 4 hits, else two binary searches); the offsets by a prefix scan of the counts; then the
+  // hits written in hit order, lane l taking hit base + l (its position the last lane whose offset is <=
+  // the hit, a binary search over the lanes), so each store instruction covers 64 consecutive hits.
+  // rmap[q]: the first hit of q's range (0: none).  The sweep's chunk metadata is one round of
+  // independent loads.
+  int* fp = reinterpret_cast<int*>(S + so.lh);
   uint32_t* mapsa = reinterpret_cast<uint32_t*>(S + so.maps);
   int* sca = reinterpret_cast<int*>(S + so.sc);
-  // zeroed records only for the calls s2c walks through its LDS link table (its loader reads every
-  // record); the others keep just the chrpos and a zero score per hit (the sweep writes what it scores)
-  const bool records = T <= kS2cCap && nq <= 65536;
   uint32_t* rmapa = reinterpret_cast<uint32_t*>(diff);  // (the coverage is done with diff)
+  const uint32_t* __restrict__ tb = table_all + O.table_offset;  // (mappings relative to the call's table)
+  wave_sync();
+  int q0 = -1;
+  for (int cb = qstart & ~63; cb <= qend && q0 < 0; cb += 64) {
+    const int q = cb + lane;
+    const uint64_t m = ballot(q >= qstart && q <= qend && q < nq && npq[q] > 0);
+    if (m) q0 = cb + __ffsll((long long)m) - 1;
+  }
+  // chromosome positions past 2^31 (Pairpool_push would drop them: outside the domain) are looked for among
+  // all the seeded hits, as before the compact layout: none when the window ends below 2^31 (a hit is
+  // chrinit + an offset within the window), else each position's last (largest) hit is read
+  const bool scan_big = (uint64_t)chrinit + (uint64_t)genomiclength + (uint64_t)ql + 64u >= 0x80000000ull;
   carry = 0;
   bool big = false;
-  uint32_t pmap = 0;  // the previous step's last hit (a position's hits may span two steps)
+  int wk = 0;
   for (int cb = 0; cb < ql; cb += 64) {
     const int q = cb + lane;
     const int v = q < nq ? npq[q] : 0;
-    const int incl = carry + wave_incl_sum(v, lane);
-    const int o = incl - v;
-    if (q < ql) off[q] = o;
-    const int mq = q < nq && v > 0 ? mpq[q] : 0;
+    const int mq = v > 0 ? mpq[q] : 0;
     const bool act = q <= qend && v > 0;
     const uint32_t qmn = act ? minact[q] : 0u, qmx0 = act ? maxact[q] : 0u;
     const uint32_t qmx = (qmn > 0 && qmx0 < qmn - 1) ? qmn - 1 : qmx0;
-    if (q < ql && !act) {
-      lowa[q] = higha[q] = 0;
-      rmapa[q] = 0u;
+    if (scan_big && v > 0) big |= (tb[mq + v - 1] >= 0x80000000u);
+    int low = 0, high = 0;
+    uint32_t rmap = 0u;
+    if (act) {
+      const uint32_t* __restrict__ sl = tb + mq;
+      if (v <= 4) {
+        uint32_t e[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) e[k] = k < v ? sl[k] : 0u;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          low += (k < v && e[k] < qmn) ? 1 : 0;
+          high += (k < v && e[k] <= qmx) ? 1 : 0;
+        }
+        high = max(high, low);
+        const uint32_t el = low == 0 ? e[0] : low == 1 ? e[1] : low == 2 ? e[2] : e[3];
+        rmap = high > low ? el : 0u;
+      } else {
+        int lo = 0, hi = v;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (sl[mid] < qmn) lo = mid + 1;
+          else hi = mid;
+        }
+        low = lo;
+        hi = v;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (sl[mid] <= qmx) lo = mid + 1;
+          else hi = mid;
+        }
+        high = lo;
+        rmap = high > low ? sl[low] : 0u;
+      }
+    }
+    // the sweep's work: a position's lookbacks grow with the hits of its range (each one beyond the first
+    // a full lookback); a diagonal far from the others widens those ranges over the gap
+    if (q >= qstart && q <= qend && high > low) wk += 1 + 4 * (high - low - 1);
+    int c = high - low, first_hit = mq + low;
+    if (q == q0) {  // (act: q0 <= qend and it has hits)
+      fp[0] = low;
+      fp[1] = high;
+      c = v;
+      first_hit = mq;
+    }
+    const int incl = carry + wave_incl_sum(c, lane);
+    const int o = incl - c;
+    if (q < ql) {
+      off[q] = o;
+      rmapa[q] = rmap;
     }
     const int hend = __shfl(incl, 63, 64);
     for (int base = carry; base < hend; base += 64) {
@@ -1972,37 +2049,19 @@ __global__ __launch_bounds__(64) void s2a_kernel(
         const int oj = __shfl(o, j + st, 64);
         if (oj <= h) j += st;
       }
-      const int oq = __shfl(o, j, 64), mj = __shfl(mq, j, 64), nj = __shfl(v, j, 64);
-      const uint32_t mn = (uint32_t)__shfl((int)qmn, j, 64), mx = (uint32_t)__shfl((int)qmx, j, 64);
-      const bool actj = __shfl(act ? 1 : 0, j, 64) != 0;
-      uint32_t map = 0u;
+      const int oq = __shfl(o, j, 64), fj = __shfl(first_hit, j, 64);
       if (h < hend) {
-        map = table_all[O.table_offset + mj + (h - oq)];  // (mappings relative to the call's table)
-        big |= (map >= 0x80000000u);
-        if (records) hits[h] = S2Hit{0, 0, 0, 0};  // CALLOC (a zero link: position 0's hit 0)
-        mapsa[h] = map;
+        mapsa[h] = tb[fj + (h - oq)];
         sca[h] = 0;
       }
-      uint32_t prev = (uint32_t)__shfl_up((int)map, 1, 64);
-      if (lane == 0) prev = pmap;
-      if (h < hend && actj) {
-        const int k = h - oq, qj = cb + j;
-        const bool first = k == 0, last = k == nj - 1;
-        if (map >= mn && (first || prev < mn)) {
-          lowa[qj] = k;
-          rmapa[qj] = map <= mx ? map : 0u;
-        } else if (last && map < mn) {
-          lowa[qj] = nj;
-          rmapa[qj] = 0u;
-        }
-        if (map > mx && (first || prev <= mx)) higha[qj] = k;
-        else if (last && map <= mx) higha[qj] = nj;
-      }
-      pmap = (uint32_t)__builtin_amdgcn_readlane((int)map, 63);
     }
     carry = hend;
   }
-  if (lane == 0) off[ql] = carry;
+  if (lane == 0) off[ql] = carry;  // the hits laid out (<= T)
+  // zeroed records only for the calls s2c walks through its LDS link table (its loader reads every
+  // record); the others keep just the chrpos and a zero score per hit (the sweep writes what it scores)
+  if (s2c_lds_class(T, carry, nq))
+    for (int h = lane; h < carry; h += 64) hits[h] = S2Hit{0, 0, 0, 0};  // CALLOC (a zero link: position 0's hit 0)
   if (ballot(big)) {  // chromosome positions past 2^31: Pairpool_push would drop them (outside the domain)
     if (lane == 0) {
       R.status = kS2Domain;
@@ -2011,17 +2070,8 @@ __global__ __launch_bounds__(64) void s2a_kernel(
     return;
   }
   wave_sync();
-  // the sweep's work: a position's lookbacks grow with its hits inside [minactive, maxactive] (each one
-  // beyond the first a full lookback); a diagonal far from the others widens those ranges over the gap
-  {
-    int wk = 0;
-    for (int q = qstart + lane; q <= qend; q += 64) {
-      const int d = higha[q] - lowa[q];
-      wk += d > 0 ? 1 + 4 * (d - 1) : 0;
-    }
-    wk = wave_sum_i(wk);
-    if (lane == 0) work[pos] = wk;
-  }
+  wk = wave_sum_i(wk);
+  if (lane == 0) work[pos] = wk;
 
   if (lane == 0) results[P.index] = R;  // status 2 with the query bounds: the sweep and the paths follow
 }
@@ -2093,9 +2143,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GMAPDP_S2B_W
     W.splicingp = P.splicingp;
     W.lane = lane;
     W.maxintronlen = P.maxintronlen;
-    const int* lowa = reinterpret_cast<const int*>(S + so.lh);
-    s2_sweep(W, npq, nq, lowa, lowa + (ql + 1), reinterpret_cast<const uint32_t*>(diff), qstart,
-             qend);  // low / high / rmap (s2a_kernel)
+    s2_sweep(W, npq, nq, reinterpret_cast<const int*>(S + so.lh), reinterpret_cast<const uint32_t*>(diff), qstart,
+             qend);  // q0's range / rmap (s2a_kernel)
   }
   wave_sync();
 #ifdef GMAPDP_OI_TIMING
@@ -2235,7 +2284,9 @@ __device__ S2WalkOut s2_walk_wave(const uint32_t* lql, const uint32_t* map, int 
 // cells, traceback_one, Stage2_filter_unique, convert_to_nucleotides.  Two launches over the same order:
 // kLdsWalk = false takes the calls whose link table does not fit LDS (more than kS2cCap hits: every 214-kb
 // window) with no LDS reserved, so 6 waves per SIMD run (32 KB of LDS allowed 5 per CU); kLdsWalk = true
-// takes the rest with the 32-KB link table.
+// takes the rest with the 32-KB link table.  The class goes by the seeding's hit count (s2c_lds_class), not
+// by the fewer hits laid out: with the latter every 214-kb call fits the table, and the bench step was 2 ms
+// slower at the table's 5 waves per CU.
 template <bool kLdsWalk>
 __global__ __launch_bounds__(64) void s2c_kernel(
     const DevStage2Problem* __restrict__ probs, const uint32_t* __restrict__ blocks, uint64_t nwords,
@@ -2279,7 +2330,7 @@ __global__ __launch_bounds__(64) void s2c_kernel(
   (void)diag_all; (void)counters; (void)scratch_cap; (void)paths_out; (void)path_cap; (void)pairs_out; (void)pair_cap;
   gmapdp_stage2_result R = results[P.index];
   if (R.status != kS2Chained) return;
-  if ((T <= kS2cCap && nq <= 65536) != kLdsWalk) return;  // the other launch's call
+  if (s2c_lds_class(T, off[ql], nq) != kLdsWalk) return;  // the other launch's call
   S2_MARK(12);
   const int qstart = R.diag_querystart, qend = R.diag_queryend;
   // ---- get_cells_fwd + the path loop: cells within FINAL_SCORE_TOLERANCE of the best, each the best
@@ -2398,7 +2449,7 @@ __global__ __launch_bounds__(64) void s2c_kernel(
   extern __shared__ uint32_t s2c_lds[];
   uint32_t* llq = s2c_lds;
   uint32_t* lmap = s2c_lds + kS2cCap;
-  const bool lds_walk = kLdsWalk;  // T <= kS2cCap && nq <= 65536 (checked above): 15-bit hit index, 16-bit querypos
+  const bool lds_walk = kLdsWalk;  // s2c_lds_class (checked above): 15-bit hit index, 16-bit querypos
   if (lds_walk && npaths > 0) {
     // 64 query positions per step (lane j holds off[cb + j]), their hits 64 at a time: a hit's position is
     // the last lane whose offset is <= the hit, a binary search over the lanes as in s2a_kernel's layout
