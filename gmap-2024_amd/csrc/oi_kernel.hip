@@ -20,9 +20,11 @@
 // popcount -- no 64-K count table, no hash.  A window 8-mer is one 64-bit funnel of two 16-nt genome
 // half-words (one half-word per lane and step): the reverse complement is its bitwise complement,
 // the forward oligo its 2-bit reversal.  Pass 1 counts per id (LDS atomics) and appends the hits to a
-// hit list; an exclusive scan lays out the table; pass 2 walks the hit list in descending chrpos and
-// places 64 hits at a time, each hit's rank among the step's hits of its oligo coming from a ballot
-// match on the id bits, which reproduces the reference's keep-the-nearest-`count` rule exactly.
+// hit list; the table is laid out in query order (each 8-mer's slice where the query first uses it: the
+// consumers walk the table by query position), the same walk writing the per-position mappings; pass 2
+// walks the hit list in descending chrpos and places 64 hits at a time, each hit's rank among the step's
+// hits of its oligo coming from a ballot match on the id bits, which reproduces the reference's
+// keep-the-nearest-`count` rule exactly.
 // oi_map_kernel (1 KB of LDS, so many waves per CU) sorts the hits by diagonal and evaluates each
 // diagonal's state machine with segmented scans (oi_mappings_sorted); a problem that does not fit the
 // batch's event pool walks the query sequentially instead.
@@ -635,7 +637,7 @@ __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
   const DevOligoProblem P = probs[blockIdx.x];
   uint32_t* bitmap = reinterpret_cast<uint32_t*>(smem);                  // 2048 words
   uint16_t* wrank = reinterpret_cast<uint16_t*>(smem + 4 * kOiWords);     // set bits before word w
-  CT* cnt = reinterpret_cast<CT*>(smem + 6 * kOiWords);                   // per id: count, then remaining
+  CT* cnt = reinterpret_cast<CT*>(smem + 6 * kOiWords);                   // per id: count, then remaining | placed << 8
   CT* offs = cnt + P.umax;                                                // per id: table offset
   const char* quc = quc_all + P.qoff;
   const int qlen = P.querylength;
@@ -804,30 +806,77 @@ __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
   const int n0 = nh_wave[0], n1 = nh_wave[1];
   nhits = n0 + n1;
   if (nhits_out && tid == 0) nhits_out[P.index] = nhits;  // the hit list's length (a plan's sizing run)
-  // Count_T wraps; the table slices follow oligo order (wave 0; the total to both waves)
+  // Count_T wraps: each id's kept count, count & 255 (the bits above it: the layout's "placed" flag)
+  for (int u = tid; u < U; u += 64 * kOiWaves) cnt[u] = (CT)((uint32_t)cnt[u] & 255u);
+  __syncthreads();
+  // The table slices follow QUERY order (wave 0; the total to both waves): the query positions in order, 64
+  // at a time, each id's slice placed where the query first uses it, so that the consumers, which walk the
+  // table by query position, read it front to back (a random read's positions are nearly all first uses).
+  // Every id is some query position's (the bitmap is built from the query), so every id gets its offset.
+  // First use, exactly: across steps by the placed flag beside the id's count, within a step the lowest lane
+  // of the id (ballot match on the id bits, as pass 2 ranks its hits).
+  // The kept counts and the offsets are all get_mappings' per-position values need (nhits of lookup, :34074),
+  // so the same walk writes them: per querypos nhits and the table offset (relative to the problem's table),
+  // cum_nohits as an inclusive prefix count of the positions whose 8-mer has no hit (a position without a
+  // full 8-mer carries it forward).  mpq holds each position's 8-mer until here.
   __shared__ uint32_t tot_s;
+  const int idbits = U > 1 ? 32 - __clz(U - 1) : 1;
+  int* cum = reinterpret_cast<int*>(base_s);
+  int totalpositions = 0;
   if (wave == 0) {
     uint32_t tot = 0;
-    for (int base = 0; base < U; base += 64) {
-      const int u = base + lane;
-      const uint32_t c = u < U ? ((uint32_t)cnt[u] & 255u) : 0u;
-      const uint32_t incl = (uint32_t)wave_scan_add(lane, (int)c);
-      if (u < U) {
-        offs[u] = (CT)(tot + incl - c);
-        cnt[u] = (CT)c;
+    int cumrun = 0;
+    for (int sb = 0; sb < nq; sb += 4 * 64) {  // 256 query positions per step, loads issued together
+      int mm[4];
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int i = sb + 64 * r + lane;
+        mm[r] = i < nq ? mpq[i] : -1;
       }
-      tot += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        if (sb + 64 * r >= nq) break;
+        const int i = sb + 64 * r + lane;
+        int id = -1;
+        uint32_t cv = 0;
+        if (mm[r] >= 0) {
+          bool in;
+          id = oligo_id(bitmap, wrank, (uint32_t)mm[r], in);
+          cv = (uint32_t)cnt[id];  // every lane reads before the first lane of each id sets the flag
+        }
+        const bool cand = id >= 0 && (cv >> 8) == 0u;
+        uint64_t eq = ballot(cand);
+        for (int b = 0; b < idbits; b++) {
+          const uint64_t m = ballot((id >> b) & 1);
+          eq &= ((id >> b) & 1) ? m : ~m;
+        }
+        const bool first = cand && lanes_below(eq, lane) == 0;
+        const uint32_t kept = cv & 255u;
+        const uint32_t c = first ? kept : 0u;
+        const uint32_t incl = (uint32_t)wave_scan_add(lane, (int)c);
+        if (first) {
+          offs[id] = (CT)(tot + incl - c);
+          cnt[id] = (CT)(cv | 0x100u);
+        }
+        tot += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        oi_wave_sync();
+        int nh = -1;
+        if (i < nq) {
+          int mo = -1;
+          if (id >= 0) {
+            nh = (int)kept;
+            npq[i] = nh;
+            if (nh > 0) mo = (int32_t)(uint32_t)offs[id];
+          }
+          mpq[i] = mo;
+        }
+        const int cincl = wave_scan_add(lane, nh == 0 ? 1 : 0);
+        if (i < nq) cum[i] = cumrun + cincl;
+        cumrun += __builtin_amdgcn_readlane(cincl, 63);
+        totalpositions += __builtin_amdgcn_readlane(wave_scan_add(lane, nh > 0 ? nh : 0), 63);
+      }
     }
     if (lane == 0) tot_s = tot;
-  }
-  // each query position's 8-mer as its id (get_mappings' lookups), so that the bitmap and its ranks are free
-  // for pass 2's table staging
-  for (int i = tid; i < nq; i += 64 * kOiWaves) {
-    const int m = mpq[i];
-    if (m >= 0) {
-      bool in;
-      mpq[i] = oligo_id(bitmap, wrank, (uint32_t)m, in);
-    }
   }
   __syncthreads();
   const uint32_t tot = tot_s;
@@ -847,44 +896,68 @@ __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
   uint32_t* table = table_all + P.table_offset;
   uint32_t* slotarr = hitlist32 + P.hit_cap;
   const uint32_t chrpos0 = P.plusp ? P.chrstart : (P.chrhigh - P.chroffset) - P.chrend;
-  const int idbits = U > 1 ? 32 - __clz(U - 1) : 1;
   __threadfence_block();
-  for (int c = 0; wave == 0 && c < nhits; c += 64) {
-    const int sl = c + lane;  // sl-th hit in store order: plus walks the list backwards
-    int id = -1;
-    uint32_t k = 0, at = 0;
-    if (sl < nhits) {
-      // ascending position: wave 0's list, then wave 1's from the list's end backwards
-      const int a = P.plusp ? nhits - 1 - sl : sl;
-      at = a < n0 ? (uint32_t)a : P.hit_cap - 1 - (uint32_t)(a - n0);
-      if (compact) {
-        const uint32_t e = hitlist32[at];
-        k = e >> 14;
-        id = (int)(e & 0x3FFFu);
-      } else {
-        const uint2 hv = hitlist[at];
-        k = hv.x;
-        id = (int)hv.y;
+  // 256 hits per step: their list entries are loaded together, a step ahead of their placement (the
+  // placement itself is sequential -- every chunk of 64 counts the ids' remaining slots down -- so a load
+  // per chunk left the wave waiting on a round trip 64 hits at a time)
+  constexpr int kP2 = 4;
+  uint32_t at_n[kP2];
+  uint2 hv_n[kP2];
+  auto load_hits = [&](int c0) {  // the sl-th hit in store order: plus walks the list backwards
+#pragma unroll
+    for (int r = 0; r < kP2; r++) {
+      const int sl = c0 + 64 * r + lane;
+      at_n[r] = 0;
+      hv_n[r] = make_uint2(0u, 0xFFFFFFFFu);
+      if (wave == 0 && sl < nhits) {
+        // ascending position: wave 0's list, then wave 1's from the list's end backwards
+        const int a = P.plusp ? nhits - 1 - sl : sl;
+        const uint32_t at = a < n0 ? (uint32_t)a : P.hit_cap - 1 - (uint32_t)(a - n0);
+        at_n[r] = at;
+        if (compact) {
+          const uint32_t e = hitlist32[at];
+          hv_n[r] = make_uint2(e >> 14, e & 0x3FFFu);
+        } else {
+          hv_n[r] = hitlist[at];
+        }
       }
     }
-    const uint64_t hits = ballot(id >= 0);
-    // lane order = store order: a hit's rank among the chunk's hits of its oligo (ballot match on the
-    // id bits) is how many of that oligo's remaining slots the lower lanes take first
-    uint64_t eq = hits;
-    for (int b = 0; b < idbits; b++) {
-      const uint64_t m = ballot((id >> b) & 1);
-      eq &= ((id >> b) & 1) ? m : ~m;
+  };
+  load_hits(0);
+  for (int c0 = 0; wave == 0 && c0 < nhits; c0 += 64 * kP2) {
+    uint32_t at_c[kP2];
+    uint2 hv_c[kP2];
+#pragma unroll
+    for (int r = 0; r < kP2; r++) {
+      at_c[r] = at_n[r];
+      hv_c[r] = hv_n[r];
     }
-    if (id >= 0) {
-      const int rank = lanes_below(eq, lane);
-      const int same = __popcll(eq);
-      const int r0 = (int)cnt[id];  // every lane reads before the first lane of each oligo writes
-      const uint32_t slot = (uint32_t)offs[id] + (uint32_t)(r0 - rank - 1);
-      if (kOiStage && compact)
-        slotarr[at] = r0 - rank > 0 ? slot : 0xFFFFFFFFu;
-      else if (r0 - rank > 0)
-        table[slot] = chrpos0 + (P.plusp ? k : (uint32_t)(npos - 1) - k);
-      if (rank == 0) cnt[id] = (CT)max(r0 - same, 0);
+    load_hits(c0 + 64 * kP2);
+#pragma unroll
+    for (int r = 0; r < kP2; r++) {
+      if (c0 + 64 * r >= nhits) break;
+      const uint32_t at = at_c[r], k = hv_c[r].x;
+      const int id = (int)hv_c[r].y;  // (-1: past the list's end)
+      const uint64_t hits = ballot(id >= 0);
+      // lane order = store order: a hit's rank among the chunk's hits of its oligo (ballot match on the
+      // id bits) is how many of that oligo's remaining slots the lower lanes take first
+      uint64_t eq = hits;
+      for (int b = 0; b < idbits; b++) {
+        const uint64_t m = ballot((id >> b) & 1);
+        eq &= ((id >> b) & 1) ? m : ~m;
+      }
+      if (id >= 0) {
+        const int rank = lanes_below(eq, lane);
+        const int same = __popcll(eq);
+        const uint32_t cv = (uint32_t)cnt[id];  // every lane reads before the first lane of each oligo writes
+        const int r0 = (int)(cv & 255u);        // the remaining slots (above them: the placed flag)
+        const uint32_t slot = (uint32_t)offs[id] + (uint32_t)(r0 - rank - 1);
+        if (kOiStage && compact)
+          slotarr[at] = r0 - rank > 0 ? slot : 0xFFFFFFFFu;
+        else if (r0 - rank > 0)
+          table[slot] = chrpos0 + (P.plusp ? k : (uint32_t)(npos - 1) - k);
+        if (rank == 0) cnt[id] = (CT)(cv - (uint32_t)min(same, r0));
+      }
     }
   }
   __threadfence_block();
@@ -907,57 +980,20 @@ __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
       __syncthreads();
     }
   }
-  // the per-id counts again (nhits of lookup, :34074)
   OI_MARK(3);
-  for (int u = tid; u < U; u += 64 * kOiWaves)
-    cnt[u] = (CT)((u + 1 < U ? (uint32_t)offs[u + 1] : tot) - (uint32_t)offs[u]);
   __threadfence_block();
   __syncthreads();
   if (wave) return;  // the rest runs in query order on wave 0
 
-  // ---- Oligoindex_get_mappings ----
+  // ---- Oligoindex_get_mappings (its per-position values: the layout's walk above) ----
   gmapdp_oligo_result res;
-  res.totalpositions = 0;
+  res.totalpositions = totalpositions;
   res.maxnconsecutive = 0;
   res.oned_matrix_p = 0;
   res.ndiagonals = 0;
   res.table_offset = P.table_offset;
   res.diag_offset = P.diag_offset;
   __threadfence_block();
-  // per querypos: nhits and table offset; cum_nohits as an inclusive prefix count of the positions
-  // whose 8-mer has no hit (a position without a full 8-mer carries it forward)
-  int* cum = reinterpret_cast<int*>(base_s);
-  int totalpositions = 0, cumrun = 0;
-  for (int sb = 0; sb < nq; sb += 4 * 64) {  // 256 query positions per step, loads issued together
-    int mm[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int i = sb + 64 * r + lane;
-      mm[r] = i < nq ? mpq[i] : -1;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int i = sb + 64 * r + lane;
-      const int m = mm[r];
-      int nh = -1;
-      if (i < nq) {
-        int mo = -1;
-        if (m >= 0) {
-          const int u = m;  // (the id, converted after pass 1)
-          nh = (int)cnt[u];
-          npq[i] = nh;
-          if (nh > 0) mo = (int32_t)(uint32_t)offs[u];  // relative to the problem's table
-        }
-        mpq[i] = mo;
-      }
-      const int incl = wave_scan_add(lane, nh == 0 ? 1 : 0);
-      if (i < nq) cum[i] = cumrun + incl;
-      cumrun += __builtin_amdgcn_readlane(incl, 63);
-      totalpositions += __builtin_amdgcn_readlane(wave_scan_add(lane, nh > 0 ? nh : 0), 63);
-    }
-  }
-  __threadfence_block();
-  res.totalpositions = totalpositions;
   if (lane == 0) {
     results[P.index] = res;
     // get_mappings' event pool: taken here, as the waves finish at scattered times, rather than by
