@@ -32,6 +32,7 @@
 
 #include "gmapdp_internal.h"
 #include "me_device.h"
+#include "oi_reduce.h"
 #include "pc_expand.h"
 #include "../../include/gmapdp.h"
 
@@ -100,11 +101,12 @@ hipError_t launch_s2c(int nproblems, hipStream_t stream, const DevStage2Problem*
                       const int32_t* npos, const int32_t* map, const uint32_t* table, const int32_t* diags,
                       unsigned char* scratch, unsigned long long* counters, unsigned long long scratch_cap,
                       gmapdp_stage2_result* results, gmapdp_path* paths, unsigned long long path_cap,
-                      gmapdp_path_pair* pairs, unsigned long long pair_cap, int phases = 7);
+                      gmapdp_path_pair* pairs, unsigned long long pair_cap, bool modal, int phases = 7);
 hipError_t launch_oi(bool wide, int nproblems, size_t lds, hipStream_t stream, const DevOligoProblem* probs,
                      const uint32_t* blocks, const char* quc, unsigned char* scratch, gmapdp_oligo_result* results,
                      int32_t* npos, int32_t* map, uint32_t* table, int32_t* diags, uint64_t* pool,
-                     unsigned long long* pool_counter, unsigned long long pool_cap, int32_t* nhits_out);
+                     unsigned long long* pool_counter, unsigned long long pool_cap, int32_t* nhits_out,
+                     bool modal);
 size_t scratch_bytes_oi_hits(int querylength, size_t hitcap);
 hipError_t launch_pc(const unsigned char* r0, int n0, int s0, const unsigned char* r1, int n1, int s1,
                      const gmapdp_pair* pairs, unsigned long long* offsets, unsigned char* out, hipStream_t stream);
@@ -114,7 +116,8 @@ hipError_t launch_pc_paths(const gmapdp_path* paths, const unsigned long long* n
 hipError_t launch_oi_split(int nproblems, int umax, hipStream_t stream, const DevOligoProblem* probs,
                            const uint32_t* blocks, const char* quc, unsigned char* scratch,
                            gmapdp_oligo_result* results, int32_t* npos, int32_t* map, uint32_t* table, int32_t* diags,
-                           uint64_t* pool, unsigned long long* pool_counter, unsigned long long pool_cap);
+                           uint64_t* pool, unsigned long long* pool_counter, unsigned long long pool_cap,
+                           bool modal);
 hipError_t launch_mx_search(int n, hipStream_t s, const gmapdp_microexon_problem* probs, const uint32_t* blocks,
                             uint64_t nwords, const char* qseq, const char* qseq_uc, gmapdp_microexon_result* results,
                             gmapdp_microexon_candidate* cands, unsigned long long cap, unsigned long long* counter,
@@ -2988,6 +2991,9 @@ struct gmapdp_oligo_plan {
   // dropped right after the run, and a fresh hipMalloc of that size per plan took up to a second.
   bool borrowed = false, sizing = false;
   std::vector<DevOligoProblem> ord;
+  // the Mode_T of the context that made the plan: its descriptors carry that mode's genome reduction, and
+  // a plan of a cmet / atoi / ttoc context runs the reducing instantiations of the scan kernels
+  int mode = 0;
 };
 
 static constexpr int kOligoChunkProblems = 16384;
@@ -3099,6 +3105,9 @@ static int oligo_plan_build(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problem
                             size_t qbytes, gmapdp_oligo_plan** plan, bool borrow, bool sizing = false) {
   if (!ctx || !plan || n < 0 || (n > 0 && (!problems || !qseq_uc))) return GMAPDP_EINVAL;
   *plan = nullptr;
+  // stage 2 exists in STANDARD and the three stranded modes; GMAP itself refuses the non-stranded ones
+  if (oi_reduction_of(ctx->mode, true) < 0)
+    return bad(ctx, "stage 2 in a non-stranded cmet / atoi / ttoc mode (GMAP supports the stranded modes only)");
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   (void)hipSetDevice(ctx->device);
   std::vector<DevOligoProblem> dev(n);
@@ -3153,6 +3162,7 @@ static int oligo_plan_build(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problem
     d.minor = p.minor ? 1 : 0;
     d.umax = umax;
     d.index = i;
+    d.reduce = oi_reduction_of(ctx->mode, p.plusp != 0);
     tcap[i] = oligo_table_cap(p);
     dcap[i] = oligo_diag_cap(p);
     toff += tcap[i];
@@ -3164,6 +3174,7 @@ static int oligo_plan_build(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problem
   }
   gmapdp_oligo_plan* P = new gmapdp_oligo_plan();
   P->n = n;
+  P->mode = ctx->mode;
   P->split = borrow;
   P->borrowed = borrow || sizing;
   P->sizing = sizing;
@@ -3267,9 +3278,11 @@ int gmapdp_oligo_plan_run(gmapdp_ctx* ctx, const gmapdp_oligo_plan* plan, const 
                           gmapdp_oligo_result* d_results, int32_t* d_npositions, int32_t* d_mappings,
                           uint32_t* d_positions, int32_t* d_diagonals, void* stream) {
   if (!ctx || !plan) return GMAPDP_EINVAL;
+  if (plan->mode != ctx->mode) return bad(ctx, "an oligo plan made by a context of another mode");
   if (plan->n == 0) return GMAPDP_OK;
   (void)hipSetDevice(ctx->device);
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  const bool modal = plan->mode != 0;
   for (size_t li = 0; li < plan->launches.size(); li++) {
     // the chunks reuse one scratch and one pool, in stream order
     if (hipMemsetAsync(plan->d_pool_counter, 0, sizeof(unsigned long long), s) != hipSuccess)
@@ -3280,10 +3293,10 @@ int gmapdp_oligo_plan_run(gmapdp_ctx* ctx, const gmapdp_oligo_plan* plan, const 
             ? launch_oi(key & 1, plan->launches[li].second, lds_bytes_oi(key >> 1, key & 1), s,
                         plan->d_probs + plan->launches[li].first, ctx->d_genome, d_qseq_uc, plan->d_scratch,
                         d_results, d_npositions, d_mappings, d_positions, d_diagonals, plan->d_pool,
-                        plan->d_pool_counter, plan->pool_cap, plan->d_nhits)
+                        plan->d_pool_counter, plan->pool_cap, plan->d_nhits, modal)
             : launch_oi_split(plan->launches[li].second, key >> 1, s, plan->d_probs + plan->launches[li].first,
                               ctx->d_genome, d_qseq_uc, plan->d_scratch, d_results, d_npositions, d_mappings,
-                              d_positions, d_diagonals, plan->d_pool, plan->d_pool_counter, plan->pool_cap);
+                              d_positions, d_diagonals, plan->d_pool, plan->d_pool_counter, plan->pool_cap, modal);
     if (e != hipSuccess) return fail(ctx, GMAPDP_ELAUNCH, "oligo launch: %s", e);
   }
   return GMAPDP_OK;
@@ -3458,7 +3471,7 @@ extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem*
                      (const int32_t*)ctx->odiag.p, (unsigned char*)ctx->s2scratch.p,
                      (unsigned long long*)ctx->s2counters.p, (unsigned long long)scratch,
                      (gmapdp_stage2_result*)ctx->s2results.p, (gmapdp_path*)ctx->s2paths.p, pcap,
-                     (gmapdp_path_pair*)ctx->s2pairs.p, qcap);
+                     (gmapdp_path_pair*)ctx->s2pairs.p, qcap, ctx->mode != 0);
     unsigned long long cnt[4] = {0, 0, 0, 0};
     if (e == hipSuccess)
       e = hipMemcpyAsync(results, ctx->s2results.p, sizeof(gmapdp_stage2_result) * n, hipMemcpyDeviceToHost, s);
@@ -4098,6 +4111,8 @@ static void stage2_plan_free(gmapdp_stage2_plan* p) {
 
 static int stage2_plan_launch(gmapdp_ctx* ctx, const gmapdp_stage2_plan* P, const char* d_qseq, const char* d_qseq_uc,
                               gmapdp_stage2_result* d_results, hipStream_t s, bool seed, int chain) {
+  // (the plan's seeding descriptors and its choice of s2c_kernel follow the mode of the context that made it)
+  if (P->oplan->mode != ctx->mode) return bad(ctx, "a stage-2 plan made by a context of another mode");
   if (seed) {
     // (no clearing of d_npos / d_map: the seeding kernels write npositions 0 and the 8-mer of every query
     // position of every call before anything reads them, and nothing reads outside the calls' slices)
@@ -4109,7 +4124,8 @@ static int stage2_plan_launch(gmapdp_ctx* ctx, const gmapdp_stage2_plan* P, cons
       return fail(ctx, GMAPDP_ELAUNCH, "stage-2 plan: %s", hipGetLastError());
     hipError_t e = launch_s2c(P->n, s, P->d_probs, ctx->d_genome, ctx->genome_words, d_qseq, d_qseq_uc, P->d_ores,
                               P->d_npos, P->d_map, P->d_table, P->d_diag, P->d_scratch, P->d_counters, P->scratch,
-                              d_results, P->d_paths, P->path_cap, P->d_pairs, P->pair_cap, chain);
+                              d_results, P->d_paths, P->path_cap, P->d_pairs, P->pair_cap, P->oplan->mode != 0,
+                              chain);
     if (e != hipSuccess) return fail(ctx, GMAPDP_ELAUNCH, "stage-2 chaining launch: %s", e);
   }
   return GMAPDP_OK;

@@ -182,7 +182,7 @@ struct DevOligoProblem {
   // needs more (a plan re-laid out from a measured run and then run on another query) reports overflow
   // (oned_matrix_p -1, Stage2_compute status -2) instead of writing past its slices.
   uint32_t hit_cap, table_cap, diag_cap;
-  int32_t pad_;
+  int32_t reduce;         // OiReduction (oi_reduce.h) of the window's genome words: the context's mode and plusp
 };
 
 // Stage2_compute descriptor (stage2.c:6325): the seeding problem's results slot plus the chaining

@@ -31,6 +31,7 @@
 #include <cstdlib>
 
 #include "dp_device.h"
+#include "oi_reduce.h"
 
 namespace gmapdp {
 
@@ -628,7 +629,9 @@ constexpr bool kOiStage = false;
       unsigned char *__restrict__ scratch, gmapdp_oligo_result *__restrict__ results,                             \
       int32_t *__restrict__ npos_out, int32_t *__restrict__ map_out, uint32_t *__restrict__ table_all,            \
       unsigned long long *__restrict__ pool_counter, unsigned long long pool_cap, int32_t *__restrict__ nhits_out
-template <typename CT>
+// kModal: a cmet / atoi / ttoc context's instantiation, which reduces every genome word pair (P.reduce,
+// oi_reduce.h) before the strand handling; the STANDARD one carries none of it.
+template <typename CT, bool kModal>
 __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int nh_wave[kOiWaves];  // each wave's pass-1 hits
@@ -735,8 +738,10 @@ __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
       pw1[a] = hh <= hhi ? half_word(blocks, hh + 1) : 0u;
     }
     // one step: the lane's 16 8-mer starts of half-word h (v = half-words h, h + 1)
+    const OiReduceMasks red = oi_reduce_masks(kModal ? P.reduce : kRedNone);
     auto step = [&](uint64_t hb, uint64_t v) {
       const uint64_t h = hb + lane;
+      if constexpr (kModal) v = oi_reduce64(v, red);  // the forward-strand words, as the reference's tally
       // the 8-mer at window offset j as its oligo: plus strand, first nt most significant (the 2-bit groups
       // of the 32 nt reversed once, then m_j = bits 2 (24 - j) ..); minus strand, the complement as read
       uint64_t vv;
@@ -1151,14 +1156,14 @@ __device__ void oi_mappings_global(int lane, const DevOligoProblem& P, unsigned 
 
 // The plan runs' kernel, and the same code under another name for a stage-2 plan's sizing run (nhits_out
 // set), so that a profile of the bench tells the plan's one-time sizing dispatches from its step's.
-template <typename CT>
+template <typename CT, bool kModal>
 __global__ __launch_bounds__(64 * kOiWaves) void oi_kernel(OI_PASS_ARGS) {
-  oi_pass<CT>(probs, blocks, quc_all, scratch, results, npos_out, map_out, table_all, pool_counter, pool_cap,
+  oi_pass<CT, kModal>(probs, blocks, quc_all, scratch, results, npos_out, map_out, table_all, pool_counter, pool_cap,
               nhits_out);
 }
-template <typename CT>
+template <typename CT, bool kModal>
 __global__ __launch_bounds__(64 * kOiWaves) void oi_size_kernel(OI_PASS_ARGS) {
-  oi_pass<CT>(probs, blocks, quc_all, scratch, results, npos_out, map_out, table_all, pool_counter, pool_cap,
+  oi_pass<CT, kModal>(probs, blocks, quc_all, scratch, results, npos_out, map_out, table_all, pool_counter, pool_cap,
               nhits_out);
 }
 
@@ -1267,6 +1272,7 @@ __device__ __forceinline__ OiWindow oi_window(const DevOligoProblem& P) {
   return w;
 }
 
+template <bool kModal>  // (see oi_pass)
 __global__ __launch_bounds__(64 * kOiWaves) void oi_scan_kernel(
     const DevOligoProblem* __restrict__ probs, const uint32_t* __restrict__ blocks, const char* __restrict__ quc_all,
     unsigned char* __restrict__ scratch, int32_t* __restrict__ npos_out, int32_t* __restrict__ map_out) {
@@ -1330,8 +1336,10 @@ __global__ __launch_bounds__(64 * kOiWaves) void oi_scan_kernel(
       pw0[a] = hh <= hhi ? half_word(blocks, hh) : 0u;
       pw1[a] = hh <= hhi ? half_word(blocks, hh + 1) : 0u;
     }
+    const OiReduceMasks red = oi_reduce_masks(kModal ? P.reduce : kRedNone);
     auto step = [&](uint64_t hb, uint64_t v) {
       const uint64_t h = hb + lane;
+      if constexpr (kModal) v = oi_reduce64(v, red);  // (see oi_pass)
       uint64_t vv;  // plus strand: the 2-bit groups of the 32 nt reversed once; minus: the complement as read
       if (P.plusp) {
         vv = ((v >> 2) & 0x3333333333333333ull) | ((v & 0x3333333333333333ull) << 2);
@@ -1772,7 +1780,8 @@ size_t lds_bytes_oib(int umax, int* tcap) {
 hipError_t launch_oi_split(int nproblems, int umax, hipStream_t stream, const DevOligoProblem* probs,
                            const uint32_t* blocks, const char* quc, unsigned char* scratch,
                            gmapdp_oligo_result* results, int32_t* npos, int32_t* map, uint32_t* table, int32_t* diags,
-                           uint64_t* pool, unsigned long long* pool_counter, unsigned long long pool_cap) {
+                           uint64_t* pool, unsigned long long* pool_counter, unsigned long long pool_cap,
+                           bool modal) {
   int tcap = 0;
   const size_t lds = lds_bytes_oib(umax, &tcap);
   const int r2 = oib_r2_bytes(umax);
@@ -1782,8 +1791,10 @@ hipError_t launch_oi_split(int nproblems, int umax, hipStream_t stream, const De
     if (e != hipSuccess) return e;
   }
   void* args[] = {(void*)&probs, (void*)&blocks, (void*)&quc, (void*)&scratch, (void*)&npos, (void*)&map};
-  hipError_t e = hipLaunchKernel(reinterpret_cast<void*>(&oi_scan_kernel), dim3(nproblems), dim3(64 * kOiWaves), args,
-                                 0, stream);
+  // (oi_build_kernel reads the hit list, never the genome: one instantiation serves every mode)
+  hipError_t e = hipLaunchKernel(modal ? reinterpret_cast<void*>(&oi_scan_kernel<true>)
+                                       : reinterpret_cast<void*>(&oi_scan_kernel<false>),
+                                 dim3(nproblems), dim3(64 * kOiWaves), args, 0, stream);
   if (e != hipSuccess) return e;
   void* bargs[] = {(void*)&probs, (void*)&scratch, (void*)&results, (void*)&npos, (void*)&map, (void*)&table,
                    (void*)&diags, (void*)&pool, (void*)&pool_counter, (void*)&pool_cap, (void*)&r2, (void*)&tcap};
@@ -1817,12 +1828,18 @@ size_t scratch_bytes_oi_fallback(int querylength, uint32_t genomiclength) {
 hipError_t launch_oi(bool wide, int nproblems, size_t lds, hipStream_t stream, const DevOligoProblem* probs,
                      const uint32_t* blocks, const char* quc, unsigned char* scratch, gmapdp_oligo_result* results,
                      int32_t* npos, int32_t* map, uint32_t* table, int32_t* diags, uint64_t* pool,
-                     unsigned long long* pool_counter, unsigned long long pool_cap, int32_t* nhits_out) {
+                     unsigned long long* pool_counter, unsigned long long pool_cap, int32_t* nhits_out,
+                     bool modal) {
   const bool sizing = nhits_out != nullptr;  // a stage-2 plan's sizing run: the same code, its own names
-  void* fn = sizing ? (wide ? reinterpret_cast<void*>(&oi_size_kernel<uint32_t>)
-                            : reinterpret_cast<void*>(&oi_size_kernel<uint16_t>))
-                    : (wide ? reinterpret_cast<void*>(&oi_kernel<uint32_t>)
-                            : reinterpret_cast<void*>(&oi_kernel<uint16_t>));
+  // (the map kernels read the table, never the genome: one instantiation serves every mode)
+  void* fn = modal ? (sizing ? (wide ? reinterpret_cast<void*>(&oi_size_kernel<uint32_t, true>)
+                                     : reinterpret_cast<void*>(&oi_size_kernel<uint16_t, true>))
+                             : (wide ? reinterpret_cast<void*>(&oi_kernel<uint32_t, true>)
+                                     : reinterpret_cast<void*>(&oi_kernel<uint16_t, true>)))
+                   : (sizing ? (wide ? reinterpret_cast<void*>(&oi_size_kernel<uint32_t, false>)
+                                     : reinterpret_cast<void*>(&oi_size_kernel<uint16_t, false>))
+                             : (wide ? reinterpret_cast<void*>(&oi_kernel<uint32_t, false>)
+                                     : reinterpret_cast<void*>(&oi_kernel<uint16_t, false>)));
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

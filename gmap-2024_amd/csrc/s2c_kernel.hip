@@ -2287,7 +2287,10 @@ __device__ S2WalkOut s2_walk_wave(const uint32_t* lql, const uint32_t* map, int 
 // takes the rest with the 32-KB link table.  The class goes by the seeding's hit count (s2c_lds_class), not
 // by the fewer hits laid out: with the latter every 214-kb call fits the table, and the bench step was 2 ms
 // slower at the table's 5 waves per CU.
-template <bool kLdsWalk>
+// kModal: a cmet / atoi / ttoc context (convert_to_nucleotides outside STANDARD, stage2.c:5403-5452): every
+// pair's genome character is the real (unreduced) genome's, and a pair whose query character differs from
+// it carries ':' (AMBIGUOUS_COMP) instead of '|'.
+template <bool kLdsWalk, bool kModal>
 __global__ __launch_bounds__(64) void s2c_kernel(
     const DevStage2Problem* __restrict__ probs, const uint32_t* __restrict__ blocks, uint64_t nwords,
     const char* __restrict__ qseq, const char* __restrict__ quc, const gmapdp_oligo_result* __restrict__ ores,
@@ -2669,6 +2672,7 @@ __global__ __launch_bounds__(64) void s2c_kernel(
             rr.queryjump = rr.genomejump = 0;
             rr.cdna = qs[lq];
             rr.comp = '|';
+            if constexpr (kModal) rr.comp = qu[lq] == c ? '|' : ':';  // queryuc against the genome (:5405)
             rr.genome = rr.genomealt = c;
             dst[total - 1 - g++] = rr;
           }
@@ -2679,6 +2683,14 @@ __global__ __launch_bounds__(64) void s2c_kernel(
           rr.cdna = cq[k];
           rr.comp = '|';
           rr.genome = rr.genomealt = cu[k];
+          if constexpr (kModal) {
+            // the observed pair is kept only when its cdna -- the query as given, compared case-sensitively --
+            // equals the genome's character, else re-pushed with ':' (:5434-5451); kept, its genome is queryuc,
+            // which then equals that character
+            const char c = s2_genomic_nt(blocks, nwords, (uint32_t)gpos, P.chroffset, P.chrhigh, plusp);
+            rr.comp = cq[k] == c ? '|' : ':';
+            rr.genome = rr.genomealt = c;
+          }
           dst[total - 1 - g] = rr;
         }
         gen += __shfl(incl, 63, 64);
@@ -2725,7 +2737,7 @@ hipError_t launch_s2c(int nproblems, hipStream_t stream, const DevStage2Problem*
                       const int32_t* npos, const int32_t* map, const uint32_t* table, const int32_t* diags,
                       unsigned char* scratch, unsigned long long* counters, unsigned long long scratch_cap,
                       gmapdp_stage2_result* results, gmapdp_path* paths, unsigned long long path_cap,
-                      gmapdp_path_pair* pairs, unsigned long long pair_cap, int phases) {
+                      gmapdp_path_pair* pairs, unsigned long long pair_cap, bool modal, int phases) {
   void* args[] = {(void*)&probs, (void*)&blocks, (void*)&nwords, (void*)&qseq, (void*)&quc, (void*)&ores,
                   (void*)&npos, (void*)&map, (void*)&table, (void*)&diags, (void*)&scratch, (void*)&counters,
                   (void*)&scratch_cap, (void*)&results, (void*)&paths, (void*)&path_cap, (void*)&pairs,
@@ -2759,13 +2771,15 @@ hipError_t launch_s2c(int nproblems, hipStream_t stream, const DevStage2Problem*
       e = hipLaunchKernel(reinterpret_cast<void*>(&s2b_kernel), dim3(nproblems), dim3(64), args, xlds, stream);
   }
   if (e == hipSuccess && (phases & 4)) {  // the heavy calls (first in the order) without LDS, then the rest
-    e = hipLaunchKernel(reinterpret_cast<void*>(&s2c_kernel<false>), dim3(nproblems), dim3(64), args, 0, stream);
+    // (modal: a cmet / atoi / ttoc context's pair emission, convert_to_nucleotides outside STANDARD)
+    void* heavy = modal ? reinterpret_cast<void*>(&s2c_kernel<false, true>)
+                        : reinterpret_cast<void*>(&s2c_kernel<false, false>);
+    void* rest = modal ? reinterpret_cast<void*>(&s2c_kernel<true, true>)
+                       : reinterpret_cast<void*>(&s2c_kernel<true, false>);
+    e = hipLaunchKernel(heavy, dim3(nproblems), dim3(64), args, 0, stream);
     if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<void*>(&s2c_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(8 * kS2cCap));
-    if (e == hipSuccess)
-      e = hipLaunchKernel(reinterpret_cast<void*>(&s2c_kernel<true>), dim3(nproblems), dim3(64), args, 8 * kS2cCap,
-                          stream);
+      e = hipFuncSetAttribute(rest, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(8 * kS2cCap));
+    if (e == hipSuccess) e = hipLaunchKernel(rest, dim3(nproblems), dim3(64), args, 8 * kS2cCap, stream);
   }
   return e;
 }

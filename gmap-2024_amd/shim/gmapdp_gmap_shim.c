@@ -2246,13 +2246,38 @@ shim_set_inquery (const void *oligoindex, const char *queryuc, int querystart, i
   }
 }
 
+/* Stage 2 runs on the engine in STANDARD and in the stranded cmet / atoi / ttoc modes: there the engine
+   reduces the genome words of the tally as count / store_positions_{fwd,rev}_std do (per nucleotide) and
+   convert_to_nucleotides marks the pairs.  gmap itself exits on the non-stranded modes, whose tally arms
+   are not consistent between the count and the store pass (apply_mode_rev_256 tests CMET_NONSTRANDED twice,
+   oligoindex_hr.c:31051 / :31072); the shim is a library, so it refuses them by name. */
+static void
+shim_refuse_stage2_mode (const char *what) {
+  char msg[160];
+#ifdef HAVE_SSE2
+  /* The SIMD builds' tally is not the per-nucleotide rule in ttoc-stranded: count_positions_fwd_simd reduces
+     with a TTOC arm (oligoindex_hr.c:20212) and store_positions_fwd_simd's 64-nt step has none (:21135-21165),
+     so the store pass writes positions the count pass never allocated; the unmodified AVX2 program crashes
+     there (tests/golden/make_e2e_modes.py), and there is no output for a drop-in to reproduce. */
+  if (shim_mode == TTOC_STRANDED) {
+    snprintf(msg, sizeof(msg), "%s in ttoc-stranded mode in a SIMD build (count / store mismatch, "
+             "oligoindex_hr.c:20212 vs :21135-21165)", what);
+    shim_refuse(msg);
+  }
+#endif
+  if (shim_mode == STANDARD || shim_mode == CMET_STRANDED || shim_mode == ATOI_STRANDED || shim_mode == TTOC_STRANDED)
+    return;
+  snprintf(msg, sizeof(msg), "%s in a non-stranded cmet / atoi / ttoc mode (oligoindex_hr.c:31051 / :31072)", what);
+  shim_refuse(msg);
+}
+
 void
 __wrap_Oligoindex_hr_tally (Oligoindex_T this, Univcoord_T mappingstart, Univcoord_T mappingend, bool plusp,
                             char *queryuc_ptr, int querystart, int queryend, Chrpos_T chrpos, Genome_T genome,
                             int genestrand) {
   (void) queryuc_ptr;
   (void) genestrand;
-  if (shim_mode != 0) shim_refuse("stage-2 seeding outside STANDARD mode (cmet / atoi / ttoc reductions)");
+  shim_refuse_stage2_mode("stage-2 seeding");
   if (this->indexsize != 8) shim_refuse("an oligoindex with indexsize other than 8");
   shim_tally.oligoindex = this;
   shim_tally.mappingstart = mappingstart;
@@ -2449,7 +2474,8 @@ __wrap_Stage2_compute (char *queryseq_ptr, char *queryuc_ptr, int querylength, i
   (void) cellpool;
   (void) stopwatch;
   (void) genestrand;
-  if (s2_mode != 0 || shim_mode != 0) shim_refuse("Stage2_compute outside STANDARD mode (cmet / atoi / ttoc)");
+  if (s2_mode != shim_mode) shim_refuse("Stage2_setup and Dynprog_init given different modes");
+  shim_refuse_stage2_mode("Stage2_compute");
   if (s2_cross_species_p) shim_refuse("Stage2_compute with cross-species canonical scoring");
   if (s2_snps_p || (genomealt != NULL && genomealt != genome)) shim_refuse("Stage2_compute with an SNP genome");
   if (s2_sufflookback != 60 || s2_nsufflookback != 5) shim_refuse("Stage2_compute with non-default lookback");

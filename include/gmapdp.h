@@ -532,7 +532,13 @@ void gmapdp_microexon_plan_destroy (gmapdp_microexon_plan *plan);
  * at chroffset..chrhigh on the plus (plusp) or minus strand.  minor selects
  * Oligoindex_array_new_minor's index (diag_lookback 60, suffnconsecutive 10) instead of the major
  * one (120, 20).  Domain: querylength > 8 (Oligoindex_set_inquery leaves stale state below that)
- * and at most 16384 distinct query 8-mers. */
+ * and at most 16384 distinct query 8-mers.
+ * The context's mode (gmapdp_create) is the tally's: STANDARD, or a stranded cmet / atoi / ttoc mode
+ * (Mode_T 1, 3, 5), in which the window's genome words are reduced before the 8-mers are taken
+ * (count / store_positions_{fwd,rev}_std, oligoindex_hr.c:19293 / :30795; the query is not reduced).
+ * In a context of a non-stranded mode (2, 4, 6: GMAP itself refuses them) every stage-2 entry point
+ * -- this batch, gmapdp_stage2_batch and both plans -- returns GMAPDP_EINVAL.  A plan runs only on a
+ * context of the mode of the one that made it. */
 typedef struct {
   int32_t qoff;
   int32_t querylength;
@@ -593,8 +599,10 @@ void gmapdp_oligo_plan_destroy (gmapdp_oligo_plan *plan);
  * query_offset 0, genestrand 0, proceed_pctcoverage 0.3, the major oligoindex array (8-mers,
  * diag_lookback 120, suffnconsecutive 20), localp, skip_repetitive_p, favor_right_p false,
  * max_nalignments 10; Stage2_setup (gmap.c:6544) without cross-species canonical scoring, without SNPs,
- * STANDARD mode, sufflookback 60, nsufflookback 5.  queryseq_ptr = qseq + qoff (case as given, the
- * Pair cdna), queryuc_ptr = qseq_uc + qoff.  Domain as for gmapdp_oligo_problem: querylength > 8, and
+ * the context's mode (STANDARD or a stranded cmet / atoi / ttoc mode, see gmapdp_oligo_problem: there the
+ * pairs' genome characters are the real genome's and comp is ':' where the query character differs,
+ * convert_to_nucleotides stage2.c:5403-5452), sufflookback 60, nsufflookback 5.  queryseq_ptr = qseq + qoff
+ * (case as given, the Pair cdna), queryuc_ptr = qseq_uc + qoff.  Domain as for gmapdp_oligo_problem: querylength > 8, and
  * genomic positions below 2^31 (Pairpool_push drops negative ones; the engine does not model that). */
 typedef struct {
   int32_t qoff;
@@ -630,8 +638,8 @@ typedef struct {
   int32_t pad_;
 } gmapdp_path;
 
-/* One Pair_T of a stage-2 path (convert_to_nucleotides): querypos, genomepos, cdna, comp ('|'),
- * genome, genomealt; a gap holder (Pairpool_push_gapholder) has querypos = genomepos = -1, its
+/* One Pair_T of a stage-2 path (convert_to_nucleotides): querypos, genomepos, cdna, comp ('|'; in a
+ * stranded cmet / atoi / ttoc context ':' where the query differs from the genome), genome, genomealt; a gap holder (Pairpool_push_gapholder) has querypos = genomepos = -1, its
  * queryjump / genomejump, and blanks; ordinary pairs carry queryjump = genomejump = 0. */
 typedef struct {
   int32_t querypos;
@@ -719,7 +727,9 @@ int gmapdp_compact_path_pairs (gmapdp_ctx *ctx, const gmapdp_path *d_paths, cons
 void gmapdp_stage2_plan_destroy (gmapdp_stage2_plan *plan);
 
 /* Create a context on HIP device `device`.  mode = Mode_T (mode.h:5;
- * 0 = STANDARD).  user_* mirror Dynprog_single_setup. */
+ * 0 = STANDARD, 1 / 3 / 5 the stranded cmet / atoi / ttoc modes, 2 / 4 / 6 the non-stranded ones: the
+ * DP family in all seven, stage 2 in STANDARD and the stranded ones).  user_* mirror
+ * Dynprog_single_setup. */
 int gmapdp_create (gmapdp_ctx **ctx, int device, int mode,
                    int user_open, int user_extend, int user_dynprog_p);
 void gmapdp_destroy (gmapdp_ctx *ctx);

@@ -125,12 +125,18 @@ def main():
         return main_gg()
     if len(sys.argv) > 1 and sys.argv[1] == "s2":
         return main_s2(int(sys.argv[2]) if len(sys.argv) > 2 else 10000)
+    # --mode=M: the same reads in a context of Mode_T M (1 cmet-, 3 atoi-, 5 ttoc-stranded: the seeding over
+    # the reduced genome, more hits per 8-mer)
+    mode = 0
+    for a in [a for a in sys.argv[1:] if a.startswith("--mode=")]:
+        mode = int(a.split("=", 1)[1])
+        sys.argv.remove(a)
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
     lib = gmapdp.load_library(os.path.join(ROOT, "gmap-2024_amd", "lib", "libgmapdp_oitiming.so"))
     lib.gmapdp_debug_oi_marks.argtypes = [C.c_void_p]
     layout = W.Layout(W.CHR22)
     genome = W.make_genome(layout, seed=22)
-    eng = gmapdp.Engine(0)
+    eng = gmapdp.Engine(0, mode=mode)
     eng.set_genome(genome.tobytes())
     sh = W.CDNA2K
     op, oq = W.make_stage2(genome, layout, n, np.random.default_rng(3000), pad=sh.pad, extra=sh.stage2 - 1.0)
