@@ -108,6 +108,12 @@ hipError_t launch_oi(bool wide, int nproblems, size_t lds, hipStream_t stream, c
                      unsigned long long* pool_counter, unsigned long long pool_cap, int32_t* nhits_out,
                      bool modal);
 size_t scratch_bytes_oi_hits(int querylength, size_t hitcap);
+// Stage2_scan: one sub-batch's gather, table and scan kernels (`extra`: DevScanExtra records)
+hipError_t launch_s2scan(bool wide, bool modal, int nproblems, size_t lds, hipStream_t stream,
+                         const DevOligoProblem* probs, const void* extra, const uint32_t* blocks, const char* quc_all,
+                         char* quc_priv, unsigned char* scratch, gmapdp_oligo_result* ores, int32_t* npos, int32_t* map,
+                         uint32_t* table, int32_t* diags, uint64_t* pool, unsigned long long* pool_counter,
+                         unsigned long long pool_cap, gmapdp_scan_result* out, int32_t* overflow_flag);
 hipError_t launch_pc(const unsigned char* r0, int n0, int s0, const unsigned char* r1, int n1, int s1,
                      const gmapdp_pair* pairs, unsigned long long* offsets, unsigned char* out, hipStream_t stream);
 hipError_t launch_pc_paths(const gmapdp_path* paths, const unsigned long long* npaths, int path_cap,
@@ -3367,6 +3373,262 @@ int gmapdp_oligo_mappings_batch(gmapdp_ctx* ctx, const gmapdp_oligo_problem* pro
   oligo_plan_free(plan);
   if (e != hipSuccess) return fail(ctx, GMAPDP_ELAUNCH, "oligo execution: %s", e);
   oligo_absolute_mappings(problems, n, results, mappings);
+  return GMAPDP_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Stage2_scan (stage2.c:5610): the seeding with the major index and Diag_update_coverage,
+// nothing but the 16-byte result leaving the device (s2scan_kernel.hip).
+// ---------------------------------------------------------------------------
+// One sub-batch's carve of the plan's arena (byte offsets): every problem's seeding scratch (main region, then
+// the sequential walk's), the event pool, the table, the diagonal records, the private query arena with the
+// per-position arrays keyed like it, the seeding's result records.
+struct ScanLaunch {
+  int first = 0, count = 0, key = 0;          // problems [first, first + count) of launch class `key`
+  unsigned long long pool_slots = 0;
+  size_t scratch = 0, pool = 0, table = 0, diag = 0, quc = 0, npos = 0, map = 0, ores = 0, total = 0;
+};
+struct gmapdp_scan_plan {
+  int n = 0, mode = 0;
+  DevOligoProblem* d_probs = nullptr;
+  unsigned char* d_extra = nullptr;           // DevScanExtra per problem, launch order
+  unsigned char* d_arena = nullptr;           // arena_bytes + the pool cursor + the overflow flag
+  size_t arena_bytes = 0, budget = 0;
+  std::vector<ScanLaunch> launches;
+};
+
+// The budget's floor: a sub-batch should fill the GPU's 256 CUs several times over at the shapes GMAP
+// scans.  A 2-kb read on a 214-kb gregion takes ~8.5 MB of worst-case scratch (hit list 1.7 MB, the
+// sequential walk's states 5.4 MB, table 0.9 MB, diagonal records 0.8 MB), so 8 GiB is ~950 such regions
+// per sub-batch, under 3 % of the MI355X's HBM; a plan allocates only what its largest sub-batch needs.
+static constexpr size_t kScanBudgetFloor = size_t(8) << 30;
+
+static size_t scan_budget(gmapdp_ctx* ctx) {
+  if (const char* ev = std::getenv("GMAPDP_SCAN_ARENA_MB")) return (size_t)std::strtoull(ev, nullptr, 10) << 20;
+  size_t held = 0;
+  for (const DevBuf* b : {&ctx->oscratch, &ctx->opool, &ctx->otable, &ctx->odiag, &ctx->onpos, &ctx->omap})
+    held += b->cap;
+  return std::max(held, kScanBudgetFloor);
+}
+
+static void scan_plan_free(gmapdp_scan_plan* p) {
+  if (!p) return;
+  if (p->d_probs) (void)hipFree(p->d_probs);
+  if (p->d_extra) (void)hipFree(p->d_extra);
+  if (p->d_arena) (void)hipFree(p->d_arena);
+  delete p;
+}
+
+extern "C" {
+
+int gmapdp_scan_plan_create(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problems, int n, const char* qseq_uc,
+                            size_t qbytes, gmapdp_scan_plan** plan) {
+  if (!ctx || !plan || n < 0 || (n > 0 && (!problems || !qseq_uc))) return GMAPDP_EINVAL;
+  *plan = nullptr;
+  if (oi_reduction_of(ctx->mode, true) < 0)
+    return bad(ctx, "stage 2 in a non-stranded cmet / atoi / ttoc mode (GMAP supports the stranded modes only)");
+  if (!ctx->d_genome) return GMAPDP_ENOGENOME;
+  (void)hipSetDevice(ctx->device);
+  // validation, distinct 8-mers and launch classes as the seeding plans make them (oligo_plan_build)
+  std::vector<int> distinct(n, 0);
+  std::vector<const char*> rej(n, nullptr);
+  plan_parallel((size_t)n, plan_threads((size_t)n * 128), [&](size_t lo, size_t hi, int) {
+    std::vector<uint32_t> bm(2048, 0u);
+    for (size_t i = lo; i < hi; i++) {
+      const gmapdp_oligo_problem& p = problems[i];
+      if (p.minor)
+        rej[i] = "Stage2_scan takes the major oligoindex only (minor must be 0)";
+      else if (p.querylength <= 8)
+        rej[i] = "stage-2 seeding needs querylength > 8 (Oligoindex_set_inquery)";
+      else if (p.qoff < 0 || (size_t)p.qoff + (size_t)p.querylength > qbytes)
+        rej[i] = "query outside the arena";
+      else
+        distinct[i] = oligo_distinct(qseq_uc + p.qoff, p.querylength, bm);
+    }
+  });
+  static const int kBuckets[] = {1024, 2048, 4096, 8192, 16384};
+  std::map<int, std::vector<int>> classes;
+  for (int i = 0; i < n; i++) {
+    const gmapdp_oligo_problem& p = problems[i];
+    if (rej[i]) return bad(ctx, rej[i]);
+    const uint64_t win = oligo_window(p);
+    if (win > 0) {
+      const uint64_t lpl = (uint64_t)p.chroffset + p.chrend + (p.plusp ? 0 : 1) - 8;
+      const uint64_t h = (lpl >> 4) + 1;
+      if (3 * (h >> 1) + 1 >= ctx->genome_words) return bad(ctx, "stage-2 window past the genome");
+    }
+    if (distinct[i] > kOligoMaxDistinct) return bad(ctx, "query with more than 16384 distinct 8-mers");
+    int umax = kBuckets[0];
+    for (int b : kBuckets)
+      if (distinct[i] <= b) { umax = b; break; }
+    classes[2 * umax + (win >= 65536 ? 1 : 0)].push_back(i);
+  }
+  gmapdp_scan_plan* P = new gmapdp_scan_plan();
+  P->n = n;
+  P->mode = ctx->mode;
+  P->budget = scan_budget(ctx);
+  struct Extra { int32_t src_qoff, out_index; };  // DevScanExtra (s2scan_kernel.hip)
+  std::vector<DevOligoProblem> ord;
+  std::vector<Extra> extra;
+  ord.reserve(n);
+  extra.reserve(n);
+  // running sums of the open sub-batch, per component
+  size_t cs = 0, cp = 0, ct = 0, cd = 0, cq = 0;
+  ScanLaunch L;
+  auto close = [&]() {
+    if (L.count == 0) return;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t at = off; off = align_up(off + bytes, 256); return at; };
+    L.scratch = carve(cs);
+    L.pool = carve(sizeof(uint64_t) * cp);
+    L.table = carve(sizeof(uint32_t) * ct);
+    L.diag = carve(4 * sizeof(int32_t) * cd);
+    L.quc = carve(cq);
+    L.npos = carve(sizeof(int32_t) * cq);
+    L.map = carve(sizeof(int32_t) * cq);
+    L.ores = carve(sizeof(gmapdp_oligo_result) * (size_t)L.count);
+    L.total = off;
+    L.pool_slots = cp;
+    P->arena_bytes = std::max(P->arena_bytes, off);
+    P->launches.push_back(L);
+    L = ScanLaunch();
+    L.first = (int)ord.size();
+    cs = cp = ct = cd = cq = 0;
+  };
+  for (auto& kv : classes)
+    for (int i : kv.second) {
+      const gmapdp_oligo_problem& p = problems[i];
+      const uint32_t w = p.chrend > p.chrstart ? p.chrend - p.chrstart : 0;
+      const size_t mb = align_up(scratch_bytes_oi(p.querylength, w), 256);
+      const size_t fb = align_up(scratch_bytes_oi_fallback(p.querylength, w), 256);
+      const size_t tcap = oligo_table_cap(p), dcap = oligo_diag_cap(p);
+      const uint64_t win = oligo_window(p);
+      // (the event pool's share as the seeding plans estimate it; a problem with more events than the
+      // sub-batch's pool has left walks the query sequentially in its fallback region: never an overflow)
+      const size_t est = (size_t)p.querylength * (2 + (size_t)(win >> 15)) + 256;
+      const size_t slots = 3 * std::min<size_t>(tcap, est);
+      const size_t qpad = align_up((size_t)p.querylength, 16);
+      const size_t bytes = mb + fb + 8 * slots + 4 * tcap + 16 * dcap + 9 * qpad + sizeof(gmapdp_oligo_result) + 8 * 256;
+      const size_t open = cs + 8 * cp + 4 * ct + 16 * cd + 9 * cq + sizeof(gmapdp_oligo_result) * (size_t)L.count + 8 * 256;
+      // one problem alone always fits: the budget grows to hold it
+      if (L.count > 0 && (kv.first != L.key || L.count >= kOligoChunkProblems || open + bytes > P->budget ||
+                          cq + qpad > 0x7fffffffull))
+        close();
+      if (L.count == 0) L.key = kv.first;
+      DevOligoProblem d;
+      std::memset(&d, 0, sizeof(d));
+      d.qoff = (int32_t)cq;  // the sub-batch's private query arena
+      d.querylength = p.querylength;
+      d.chrstart = p.chrstart;
+      d.chrend = p.chrend;
+      d.chroffset = p.chroffset;
+      d.chrhigh = p.chrhigh;
+      d.plusp = p.plusp ? 1 : 0;
+      d.minor = 0;
+      d.umax = kv.first >> 1;
+      d.index = L.count;     // its seeding record within the sub-batch
+      d.table_offset = (int64_t)ct;
+      d.diag_offset = (int64_t)cd;
+      d.scratch_offset = (int64_t)cs;
+      d.fallback_offset = (int64_t)(cs + mb);
+      d.hit_cap = (uint32_t)std::min<size_t>((size_t)w + 2, 0xffffffffu);
+      d.table_cap = (uint32_t)std::min<size_t>(tcap, 0xffffffffu);
+      d.diag_cap = (uint32_t)std::min<size_t>(dcap, 0xffffffffu);
+      d.reduce = oi_reduction_of(ctx->mode, p.plusp != 0);
+      ord.push_back(d);
+      extra.push_back(Extra{p.qoff, i});
+      cs += mb + fb;
+      cp += slots;
+      ct += tcap;
+      cd += dcap;
+      cq += qpad;
+      L.count++;
+    }
+  close();
+  hipError_t e = hipSuccess;
+  if (n) {
+    e = hipMalloc(&P->d_probs, sizeof(DevOligoProblem) * (size_t)n);
+    if (e == hipSuccess) e = hipMalloc(&P->d_extra, sizeof(Extra) * (size_t)n);
+    // (the pool cursor and the overflow flag follow the arena)
+    if (e == hipSuccess) e = hipMalloc(&P->d_arena, P->arena_bytes + 256);
+    if (e == hipSuccess) e = hipMemcpy(P->d_probs, ord.data(), sizeof(DevOligoProblem) * (size_t)n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(P->d_extra, extra.data(), sizeof(Extra) * (size_t)n, hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    scan_plan_free(P);
+    return fail(ctx, GMAPDP_ENOMEM, "scan plan: %s", e);
+  }
+  *plan = P;
+  return GMAPDP_OK;
+}
+
+int gmapdp_scan_plan_nlaunches(const gmapdp_scan_plan* plan) { return plan ? (int)plan->launches.size() : 0; }
+size_t gmapdp_scan_plan_scratch_bytes(const gmapdp_scan_plan* plan) { return plan ? plan->arena_bytes : 0; }
+void gmapdp_scan_plan_destroy(gmapdp_scan_plan* plan) { scan_plan_free(plan); }
+
+int gmapdp_scan_plan_run(gmapdp_ctx* ctx, const gmapdp_scan_plan* plan, const char* d_qseq_uc,
+                         gmapdp_scan_result* d_results, void* stream) {
+  if (!ctx || !plan) return GMAPDP_EINVAL;
+  if (plan->mode != ctx->mode) return bad(ctx, "a scan plan made by a context of another mode");
+  if (plan->n == 0) return GMAPDP_OK;
+  if (!d_qseq_uc || !d_results) return GMAPDP_EINVAL;
+  (void)hipSetDevice(ctx->device);
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  unsigned char* A = plan->d_arena;
+  unsigned long long* pool_counter = reinterpret_cast<unsigned long long*>(A + plan->arena_bytes);
+  int32_t* flag = reinterpret_cast<int32_t*>(A + plan->arena_bytes + 64);
+  if (hipMemsetAsync(flag, 0, sizeof(int32_t), s) != hipSuccess)
+    return fail(ctx, GMAPDP_ELAUNCH, "scan flag reset: %s", hipGetLastError());
+  for (const ScanLaunch& L : plan->launches) {
+    // the sub-batches reuse one arena, in stream order
+    const hipError_t e = launch_s2scan(
+        L.key & 1, plan->mode != 0, L.count, lds_bytes_oi(L.key >> 1, L.key & 1), s, plan->d_probs + L.first,
+        plan->d_extra + 8 * (size_t)L.first, ctx->d_genome, d_qseq_uc, reinterpret_cast<char*>(A + L.quc),
+        A + L.scratch, reinterpret_cast<gmapdp_oligo_result*>(A + L.ores), reinterpret_cast<int32_t*>(A + L.npos),
+        reinterpret_cast<int32_t*>(A + L.map), reinterpret_cast<uint32_t*>(A + L.table),
+        reinterpret_cast<int32_t*>(A + L.diag), reinterpret_cast<uint64_t*>(A + L.pool), pool_counter, L.pool_slots,
+        d_results, flag);
+    if (e != hipSuccess) return fail(ctx, GMAPDP_ELAUNCH, "scan launch: %s", e);
+  }
+  return GMAPDP_OK;
+}
+
+int gmapdp_stage2_scan_batch(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problems, int n, const char* qseq_uc,
+                             size_t qbytes, gmapdp_scan_result* results) {
+  if (!ctx || n < 0 || (n > 0 && (!problems || !results || !qseq_uc))) return GMAPDP_EINVAL;
+  gmapdp_scan_plan* plan = nullptr;
+  int rc = gmapdp_scan_plan_create(ctx, problems, n, qseq_uc, qbytes, &plan);
+  if (rc) return rc;
+  if (n == 0) {
+    scan_plan_free(plan);
+    return GMAPDP_OK;
+  }
+  hipStream_t s = ctx->stream;
+  hipError_t e = ctx->qseq_uc.ensure(qbytes);
+  if (e == hipSuccess) e = ctx->oresults.ensure(sizeof(gmapdp_scan_result) * (size_t)n);
+  if (e == hipSuccess) e = hipMemcpyAsync(ctx->qseq_uc.p, qseq_uc, qbytes, hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) {
+    scan_plan_free(plan);
+    return fail(ctx, GMAPDP_ENOMEM, "scan buffers: %s", e);
+  }
+  rc = gmapdp_scan_plan_run(ctx, plan, (const char*)ctx->qseq_uc.p, (gmapdp_scan_result*)ctx->oresults.p, nullptr);
+  int32_t overflow = 0;
+  if (rc == GMAPDP_OK) {
+    e = hipMemcpyAsync(results, ctx->oresults.p, sizeof(gmapdp_scan_result) * (size_t)n, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(&overflow, plan->d_arena + plan->arena_bytes + 64, sizeof(int32_t), hipMemcpyDeviceToHost, s);
+  }
+  const hipError_t es = ctx_sync(ctx, s);  // (also before the plan's buffers are freed)
+  scan_plan_free(plan);
+  if (rc) return rc;
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return fail(ctx, GMAPDP_ELAUNCH, "scan execution: %s", e);
+  if (overflow) {
+    ctx->err = "Stage2_scan: a problem's seeding outgrew its worst-case layout (its result is ncovered -1)";
+    return GMAPDP_ELAUNCH;
+  }
   return GMAPDP_OK;
 }
 

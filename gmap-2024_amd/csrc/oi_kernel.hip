@@ -1154,6 +1154,10 @@ __device__ void oi_mappings_global(int lane, const DevOligoProblem& P, unsigned 
   }
 }
 
+// (s2scan_kernel.hip includes this file for the device functions above and defines GMAPDP_OI_DEVICE_ONLY:
+// the kernels, the split path and the host launchers below belong to this translation unit alone)
+#ifndef GMAPDP_OI_DEVICE_ONLY
+
 // The plan runs' kernel, and the same code under another name for a stage-2 plan's sizing run (nhits_out
 // set), so that a profile of the bench tells the plan's one-time sizing dispatches from its step's.
 template <typename CT, bool kModal>
@@ -1853,5 +1857,7 @@ hipError_t launch_oi(bool wide, int nproblems, size_t lds, hipStream_t stream, c
   return hipLaunchKernel(sizing ? reinterpret_cast<void*>(&oi_size_map_kernel) : reinterpret_cast<void*>(&oi_map_kernel),
                          dim3(nproblems), dim3(64), margs, 0, stream);
 }
+
+#endif  // GMAPDP_OI_DEVICE_ONLY
 
 }  // namespace gmapdp

@@ -105,6 +105,12 @@ class OligoResult(C.Structure):
                 ("ndiagonals", C.c_int32), ("table_offset", C.c_int64), ("diag_offset", C.c_int64)]
 
 
+class ScanResult(C.Structure):
+    """gmapdp_scan_result: Stage2_scan's ncovered and *stage2_source, the seeding's diagnostics."""
+    _fields_ = [("ncovered", C.c_int32), ("stage2_source", C.c_int32), ("totalpositions", C.c_int32),
+                ("maxnconsecutive", C.c_int32)]
+
+
 class Stage2Problem(C.Structure):
     _fields_ = [("qoff", C.c_int32), ("querylength", C.c_int32), ("chrstart", C.c_uint32), ("chrend", C.c_uint32),
                 ("chroffset", C.c_uint64), ("chrhigh", C.c_uint64), ("plusp", C.c_int32), ("splicingp", C.c_int32),
@@ -149,6 +155,7 @@ SJ_PROBLEM_DTYPE = _struct_dtype(SjProblem)
 SJ_RESULT_DTYPE = _struct_dtype(SjResult)
 OLIGO_PROBLEM_DTYPE = _struct_dtype(OligoProblem)
 OLIGO_RESULT_DTYPE = _struct_dtype(OligoResult)
+SCAN_RESULT_DTYPE = _struct_dtype(ScanResult)
 STAGE2_PROBLEM_DTYPE = _struct_dtype(Stage2Problem)
 STAGE2_RESULT_DTYPE = _struct_dtype(Stage2Result)
 PATH_DTYPE = np.dtype([("pair_offset", "<i8"), ("npairs", "<i4"), ("pad_", "<i4")])
@@ -263,6 +270,13 @@ def load_library(path=LIB_PATH):
         "gmapdp_oligo_plan_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
         "gmapdp_oligo_plan_destroy": (None, [C.c_void_p]),
+        "gmapdp_stage2_scan_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+        "gmapdp_scan_plan_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                              P(C.c_void_p)]),
+        "gmapdp_scan_plan_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "gmapdp_scan_plan_nlaunches": (C.c_int, [C.c_void_p]),
+        "gmapdp_scan_plan_scratch_bytes": (C.c_size_t, [C.c_void_p]),
+        "gmapdp_scan_plan_destroy": (None, [C.c_void_p]),
         "gmapdp_stage2_plan_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                                 P(C.c_void_p)]),
         "gmapdp_stage2_plan_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -754,6 +768,45 @@ class Engine:
                         np_, plist, dg))
         return out
 
+    # -- batched Stage2_scan (seeding with the major index + Diag_update_coverage) ------------------
+    @staticmethod
+    def build_scan_batch(calls):
+        """calls: dicts (quc, chrstart, chrend, chroffset, chrhigh, plusp) -> (problems, qucbuf).  Calls that
+        carry the same `quc` object share one slice of the arena (a read's gregions)."""
+        calls = list(calls)
+        probs = np.zeros(len(calls), dtype=OLIGO_PROBLEM_DTYPE)
+        parts, off, seen = [], 0, {}
+        for i, p in enumerate(calls):
+            q = p["quc"]
+            if id(q) not in seen:
+                seen[id(q)] = off
+                parts.append(q)
+                off += len(q)
+            probs[i]["qoff"] = seen[id(q)]
+            probs[i]["querylength"] = len(q)
+            for k in ("chrstart", "chrend", "chroffset", "chrhigh", "plusp"):
+                probs[i][k] = int(p.get(k, 0))
+        return probs, (b"".join(parts) or b"\0")
+
+    def stage2_scan_batch_raw(self, probs, qucbuf):
+        """gmapdp_stage2_scan_batch -> an (n, 4) int32 array: ncovered, stage2_source, totalpositions,
+        maxnconsecutive per problem."""
+        n = len(probs)
+        out = np.zeros((n, 4), dtype=np.int32)
+        rc = self.lib.gmapdp_stage2_scan_batch(self.h, probs.ctypes.data, n, qucbuf, len(qucbuf), out.ctypes.data)
+        self._check(rc, "gmapdp_stage2_scan_batch")
+        return out
+
+    def stage2_scan_batch(self, calls):
+        """Stage2_scan per call: an (n, 4) int32 array (ncovered, stage2_source, totalpositions,
+        maxnconsecutive).  The call dicts are oligo_mappings_batch's without `minor`."""
+        probs, qucbuf = self.build_scan_batch(calls)
+        return self.stage2_scan_batch_raw(probs, qucbuf)
+
+    def scan_plan(self, probs, qucbuf):
+        """A device-resident Stage2_scan plan (gmapdp_scan_plan_create); see ScanPlan."""
+        return ScanPlan(self, probs, qucbuf)
+
     # -- batched Stage2_compute (seeding + chaining) -----------------------------------------------
     @staticmethod
     def build_stage2_batch(calls):
@@ -927,6 +980,73 @@ class Engine:
         rc = lib.gmapdp_mixed_batch(self.h, qbuf, qucbuf, len(qbuf), C.byref(m))
         out["candidates_needed"] = int(m.candidates_needed)
         return rc, out
+
+
+class ScanPlan:
+    """gmapdp_scan_plan: Stage2_scan over a fixed set of (query slice, window) problems, device-resident.
+    run() launches one pass asynchronously (on `stream`, a hipStream_t value, or the engine's stream) against
+    the plan's own device copy of the query arena (or `d_quc`, a device pointer to another arena of the same
+    layout) into the plan's result buffer (or `d_results`); results() waits for the device and returns the
+    (n, 4) int32 array.  Two runs of one plan must be ordered (one stream, or a wait in between)."""
+
+    def __init__(self, engine, probs, qucbuf):
+        self.engine, self.lib, self.n = engine, engine.lib, len(probs)
+        self.hip = _hip()
+        self.plan = C.c_void_p()
+        self._bufs = []
+        engine._check(self.lib.gmapdp_scan_plan_create(engine.h, probs.ctypes.data, self.n, qucbuf, len(qucbuf),
+                                                       C.byref(self.plan)), "gmapdp_scan_plan_create")
+        try:
+            self.d_quc = self._dbuf(len(qucbuf), qucbuf)
+            self.d_results = self._dbuf(SCAN_RESULT_DTYPE.itemsize * self.n)
+        except Exception:
+            self.close()
+            raise
+
+    def _dbuf(self, nbytes, src=None):
+        ptr = C.c_void_p()
+        if self.hip.hipMalloc(C.byref(ptr), max(nbytes, 16)) != 0:
+            raise GmapdpError("hipMalloc(%d) failed" % nbytes)
+        self._bufs.append(ptr)
+        if src is not None and self.hip.hipMemcpy(ptr, src, nbytes, 1) != 0:  # hipMemcpyHostToDevice
+            raise GmapdpError("hipMemcpy failed")
+        return ptr
+
+    @property
+    def nlaunches(self):
+        return self.lib.gmapdp_scan_plan_nlaunches(self.plan)
+
+    @property
+    def scratch_bytes(self):
+        return self.lib.gmapdp_scan_plan_scratch_bytes(self.plan)
+
+    def run(self, stream=None, d_quc=None, d_results=None):
+        self.engine._check(self.lib.gmapdp_scan_plan_run(self.engine.h, self.plan, d_quc or self.d_quc,
+                                                         d_results or self.d_results, stream),
+                           "gmapdp_scan_plan_run")
+
+    def results(self, d_results=None):
+        if self.hip.hipDeviceSynchronize() != 0:
+            raise GmapdpError("hipDeviceSynchronize failed")
+        out = np.zeros((self.n, 4), dtype=np.int32)
+        if self.n and self.hip.hipMemcpy(out.ctypes.data, d_results or self.d_results, out.nbytes, 2) != 0:
+            raise GmapdpError("hipMemcpy failed")  # (2: hipMemcpyDeviceToHost)
+        return out
+
+    def close(self):
+        if self.plan:
+            self.hip.hipDeviceSynchronize()
+            for b in self._bufs:
+                self.hip.hipFree(b)
+            self._bufs = []
+            self.lib.gmapdp_scan_plan_destroy(self.plan)
+            self.plan = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def decode_genome_results(results, pairs, dynprogindices):

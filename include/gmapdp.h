@@ -29,6 +29,8 @@
  *                            known-splice-site end alignments of Dynprog_end5/3_known (:2748/3009)
  *   gmapdp_oligo_mappings_batch  stage-2 seeding: Oligoindex_hr_tally + Oligoindex_get_mappings
  *                            (oligoindex_hr.c:33849/34127) as Stage2_compute calls them (stage2.c:6480-6495)
+ *   gmapdp_stage2_scan_batch Stage2_scan (stage2.c:5610): the seeding with the major index and
+ *                            Diag_update_coverage (diag.c:216), one 16-byte result per gregion
  *   gmapdp_stage2_batch      Stage2_compute (stage2.c:6325) as GMAP calls it (gmap.c:1208): the
  *                            seeding above, then Diag_compute_bounds (diag.c:597),
  *                            align_compute_lookback (stage2.c:4402), convert_to_nucleotides (:5334)
@@ -594,6 +596,47 @@ int gmapdp_oligo_plan_run (gmapdp_ctx *ctx, const gmapdp_oligo_plan *plan, const
                            gmapdp_oligo_result *d_results, int32_t *d_npositions, int32_t *d_mappings,
                            uint32_t *d_positions, int32_t *d_diagonals, void *stream);
 void gmapdp_oligo_plan_destroy (gmapdp_oligo_plan *plan);
+
+/* Stage2_scan (stage2.c:5610) as stage3_from_gregions calls it for every gregion before any
+ * Stage2_compute (gmap.c:1855-1899): one seeding with the major 8-mer index (diag_lookback 120,
+ * suffnconsecutive 20), coveredp all false, then Diag_update_coverage (diag.c:216).  A problem is a
+ * gmapdp_oligo_problem whose fields are Stage2_scan's arguments (query slice, window, strand); minor must
+ * be 0 (GMAPDP_EINVAL otherwise).  Domain and modes as for the seeding above: querylength > 8, STANDARD or
+ * a stranded mode, GMAPDP_EINVAL in a context of mode 2, 4 or 6, GMAPDP_ENOGENOME without a genome.
+ * Unlike gmapdp_oligo_mappings_batch, query slices may overlap or be identical (a read's gregions all point
+ * at the same qoff): the seeding's per-position state lives in per-problem scratch.
+ * chrend <= chrstart gives ncovered 0, stage2_source 1 (get_mappings returns before writing anything).
+ * Only the results leave the device.  The batch runs as sub-batches, ordered on one stream, whose
+ * worst-case scratch (table, diagonals, hit list, event pool, per-position arrays) fits a budget, so
+ * memory does not grow with n.  The budget is the number of bytes the context's grow-only seeding buffers
+ * hold when the plan is made, at least 8 GiB (~950 regions of a 2-kb read on a 214-kb gregion; a plan
+ * allocates only what its largest sub-batch needs); GMAPDP_SCAN_ARENA_MB (read at plan creation) overrides
+ * both; one problem alone always fits (the budget grows to its worst case).  The capacities are worst
+ * cases, so a seeding layout overflow cannot happen; should one be reported all the same, the problem's
+ * result is {-1, 0, totalpositions, 0} and the batch call returns GMAPDP_ELAUNCH with gmapdp_last_error
+ * set -- never a plausible-looking count. */
+typedef struct {
+  int32_t ncovered;         /* Stage2_scan's return value */
+  int32_t stage2_source;    /* *stage2_source: 1 (one 8-mer source) */
+  int32_t totalpositions;   /* the seeding's, for diagnostics */
+  int32_t maxnconsecutive;
+} gmapdp_scan_result;
+
+int gmapdp_stage2_scan_batch (gmapdp_ctx *ctx, const gmapdp_oligo_problem *problems, int n,
+                              const char *qseq_uc, size_t qbytes, gmapdp_scan_result *results);
+/* Device-resident form: plan once, then run asynchronously on `stream` (hipStream_t; NULL = the context's
+ * stream) against a device-resident upper-case query arena laid out like the one the plan was made from.
+ * d_results has n entries in problem order.  The plan owns its scratch, so its runs may overlap DP plans
+ * on other streams; two runs of one plan must be ordered.  gmapdp_scan_plan_nlaunches: the sub-batches
+ * of one run (three kernels each); _scratch_bytes: the device bytes the plan holds. */
+typedef struct gmapdp_scan_plan gmapdp_scan_plan;
+int gmapdp_scan_plan_create (gmapdp_ctx *ctx, const gmapdp_oligo_problem *problems, int n, const char *qseq_uc,
+                             size_t qbytes, gmapdp_scan_plan **plan);
+int gmapdp_scan_plan_run (gmapdp_ctx *ctx, const gmapdp_scan_plan *plan, const char *d_qseq_uc,
+                          gmapdp_scan_result *d_results, void *stream);
+int gmapdp_scan_plan_nlaunches (const gmapdp_scan_plan *plan);
+size_t gmapdp_scan_plan_scratch_bytes (const gmapdp_scan_plan *plan);
+void gmapdp_scan_plan_destroy (gmapdp_scan_plan *plan);
 
 /* Stage2_compute (stage2.c:6325) as GMAP's update_stage3middle_list calls it (gmap.c:1208-1215):
  * query_offset 0, genestrand 0, proceed_pctcoverage 0.3, the major oligoindex array (8-mers,
