@@ -101,7 +101,12 @@ hipError_t launch_s2c(int nproblems, hipStream_t stream, const DevStage2Problem*
                       const int32_t* npos, const int32_t* map, const uint32_t* table, const int32_t* diags,
                       unsigned char* scratch, unsigned long long* counters, unsigned long long scratch_cap,
                       gmapdp_stage2_result* results, gmapdp_path* paths, unsigned long long path_cap,
-                      gmapdp_path_pair* pairs, unsigned long long pair_cap, bool modal, int phases = 7);
+                      gmapdp_path_pair* pairs, unsigned long long pair_cap, bool modal, int phases = 7,
+                      const double* canon_metab = nullptr);
+int s2_canon_counters(unsigned long long* out8);
+hipError_t launch_canon_links(long long n, hipStream_t s, const uint32_t* blocks, uint64_t nwords, const double* T,
+                              const gmapdp_coord_t* prevpos, const gmapdp_coord_t* currpos, int plusp,
+                              gmapdp_coord_t chroffset, gmapdp_coord_t chrhigh, uint8_t* out);
 hipError_t launch_oi(bool wide, int nproblems, size_t lds, hipStream_t stream, const DevOligoProblem* probs,
                      const uint32_t* blocks, const char* quc, unsigned char* scratch, gmapdp_oligo_result* results,
                      int32_t* npos, int32_t* map, uint32_t* table, int32_t* diags, uint64_t* pool,
@@ -828,6 +833,29 @@ int gmapdp_maxent_sites(gmapdp_ctx* ctx, const gmapdp_coord_t* positions, const 
   if (e == hipSuccess) e = hipMemcpyAsync(out, ctx->dout.p, 8 * n, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = ctx_sync(ctx, s);
   return e == hipSuccess ? GMAPDP_OK : fail(ctx, GMAPDP_ELAUNCH, "maxent: %s", e);
+}
+
+int gmapdp_canonical_links(gmapdp_ctx* ctx, const gmapdp_coord_t* prevpos, const gmapdp_coord_t* currpos, size_t n,
+                           int plusp, gmapdp_coord_t chroffset, gmapdp_coord_t chrhigh, uint8_t* out) {
+  if (!ctx || (n && (!prevpos || !currpos || !out))) return GMAPDP_EINVAL;
+  if (!ctx->d_genome) return GMAPDP_ENOGENOME;
+  if (n == 0) return GMAPDP_OK;
+  (void)hipSetDevice(ctx->device);
+  const double* T = me_tables(ctx);
+  if (!T) return GMAPDP_EINVAL;
+  hipError_t e = ctx->din.ensure(16 * n);
+  if (e == hipSuccess) e = ctx->dout.ensure(n);
+  if (e != hipSuccess) return fail(ctx, GMAPDP_ENOMEM, "canonical-link buffers: %s", e);
+  unsigned char* din = (unsigned char*)ctx->din.p;
+  hipStream_t s = ctx->stream;
+  e = hipMemcpyAsync(din, prevpos, 8 * n, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(din + 8 * n, currpos, 8 * n, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess)
+    e = launch_canon_links((long long)n, s, ctx->d_genome, ctx->genome_words, T, (const gmapdp_coord_t*)din,
+                           (const gmapdp_coord_t*)(din + 8 * n), plusp, chroffset, chrhigh, (uint8_t*)ctx->dout.p);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, ctx->dout.p, n, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = ctx_sync(ctx, s);
+  return e == hipSuccess ? GMAPDP_OK : fail(ctx, GMAPDP_ELAUNCH, "canonical links: %s", e);
 }
 
 }  // extern "C"
@@ -3638,6 +3666,20 @@ int gmapdp_stage2_scan_batch(gmapdp_ctx* ctx, const gmapdp_oligo_problem* proble
 // Stage2_compute: seeding (oi_kernel + oi_map_kernel) then chaining (s2c_kernel)
 // on the device; one synchronous batch.
 // ---------------------------------------------------------------------------
+// gmapdp_stage2_problem.flags of a batch or plan: one value for all its calls (the sweep's variant is chosen
+// per launch).  *metab: the device MaxEnt tables when GMAPDP_S2_CANONICAL_MIDDLE is set (missing tables fail
+// as they do for genome gaps with device MaxEnt), else NULL.
+static int s2_batch_flags(gmapdp_ctx* ctx, const gmapdp_stage2_problem* problems, int n, const double** metab) {
+  *metab = nullptr;
+  for (int i = 0; i < n; i++) {
+    if (problems[i].flags & ~GMAPDP_S2_CANONICAL_MIDDLE) return bad(ctx, "stage 2: unknown bits in flags");
+    if (problems[i].flags != problems[0].flags)
+      return bad(ctx, "stage 2: one batch or plan takes one value of flags (GMAPDP_S2_CANONICAL_MIDDLE is mixed)");
+  }
+  if (n > 0 && (problems[0].flags & GMAPDP_S2_CANONICAL_MIDDLE) && !(*metab = me_tables(ctx))) return GMAPDP_EINVAL;
+  return GMAPDP_OK;
+}
+
 extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem* problems, int n, const char* qseq,
                                    const char* qseq_uc, size_t qbytes, gmapdp_stage2_result* results,
                                    gmapdp_path* paths, size_t path_cap, gmapdp_path_pair* pairs, size_t pair_cap,
@@ -3648,6 +3690,8 @@ extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem*
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   if (n == 0) return GMAPDP_OK;
   (void)hipSetDevice(ctx->device);
+  const double* canon_metab = nullptr;
+  if (int frc = s2_batch_flags(ctx, problems, n, &canon_metab)) return frc;
   std::vector<gmapdp_oligo_problem> op(n);
   std::vector<DevStage2Problem> dp(n);
   for (int i = 0; i < n; i++) {
@@ -3733,7 +3777,7 @@ extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem*
                      (const int32_t*)ctx->odiag.p, (unsigned char*)ctx->s2scratch.p,
                      (unsigned long long*)ctx->s2counters.p, (unsigned long long)scratch,
                      (gmapdp_stage2_result*)ctx->s2results.p, (gmapdp_path*)ctx->s2paths.p, pcap,
-                     (gmapdp_path_pair*)ctx->s2pairs.p, qcap, ctx->mode != 0);
+                     (gmapdp_path_pair*)ctx->s2pairs.p, qcap, ctx->mode != 0, 7, canon_metab);
     unsigned long long cnt[4] = {0, 0, 0, 0};
     if (e == hipSuccess)
       e = hipMemcpyAsync(results, ctx->s2results.p, sizeof(gmapdp_stage2_result) * n, hipMemcpyDeviceToHost, s);
@@ -4343,6 +4387,15 @@ extern "C" int gmapdp_debug_stage2_scratch(gmapdp_ctx* ctx, void* out, size_t by
   return hipMemcpy(out, ctx->s2scratch.p, bytes, hipMemcpyDeviceToHost) == hipSuccess ? GMAPDP_OK : GMAPDP_ELAUNCH;
 }
 
+// Test / measurement aid: what the cross-species sweeps (GMAPDP_S2_CANONICAL_MIDDLE) did since the last call,
+// then cleared (see include/gmapdp.h).  Synchronises the device.
+extern "C" int gmapdp_debug_canon_counters(gmapdp_ctx* ctx, unsigned long long* out8) {
+  if (!ctx || !out8) return GMAPDP_EINVAL;
+  (void)hipSetDevice(ctx->device);
+  if (hipDeviceSynchronize() != hipSuccess) return GMAPDP_ELAUNCH;
+  return s2_canon_counters(out8) ? GMAPDP_ELAUNCH : GMAPDP_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Stage2_compute, device-resident plan (bench / pipelined callers): the seeding plan plus the chaining
 // kernel's pools, sized once by running the seeding at plan time.
@@ -4359,6 +4412,7 @@ struct gmapdp_stage2_plan {
   gmapdp_path* d_paths = nullptr;
   gmapdp_path_pair* d_pairs = nullptr;
   size_t qbytes = 0, scratch = 0, path_cap = 0, pair_cap = 0;
+  const double* d_canon = nullptr;  // GMAPDP_S2_CANONICAL_MIDDLE: the MaxEnt tables of the sweep's canonical variant
 };
 
 static void stage2_plan_free(gmapdp_stage2_plan* p) {
@@ -4387,7 +4441,7 @@ static int stage2_plan_launch(gmapdp_ctx* ctx, const gmapdp_stage2_plan* P, cons
     hipError_t e = launch_s2c(P->n, s, P->d_probs, ctx->d_genome, ctx->genome_words, d_qseq, d_qseq_uc, P->d_ores,
                               P->d_npos, P->d_map, P->d_table, P->d_diag, P->d_scratch, P->d_counters, P->scratch,
                               d_results, P->d_paths, P->path_cap, P->d_pairs, P->pair_cap, P->oplan->mode != 0,
-                              chain);
+                              chain, P->d_canon);
     if (e != hipSuccess) return fail(ctx, GMAPDP_ELAUNCH, "stage-2 chaining launch: %s", e);
   }
   return GMAPDP_OK;
@@ -4401,6 +4455,8 @@ int gmapdp_stage2_plan_create(gmapdp_ctx* ctx, const gmapdp_stage2_problem* prob
   *plan = nullptr;
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   (void)hipSetDevice(ctx->device);
+  const double* canon_metab = nullptr;
+  if (int frc = s2_batch_flags(ctx, problems, n, &canon_metab)) return frc;
   std::vector<gmapdp_oligo_problem> op(n);
   std::vector<DevStage2Problem> dp(n);
   size_t qsum = 0;
@@ -4417,6 +4473,7 @@ int gmapdp_stage2_plan_create(gmapdp_ctx* ctx, const gmapdp_stage2_problem* prob
   PlanTimer tm("stage2_plan_create");
   P->n = n;
   P->qbytes = qbytes;
+  P->d_canon = canon_metab;
   int rc = oligo_plan_build(ctx, op.data(), n, qseq_uc, qbytes, &P->oplan, false, /*sizing*/ true);
   tm.mark("oligo_plan_build");
   if (rc) {

@@ -10,6 +10,7 @@
 //                    strand.  One workgroup per problem; the entries are independent (6 table loads each).
 #include "dp_device.h"
 #include "me_device.h"
+#include "canon_device.h"
 
 namespace gmapdp {
 
@@ -33,6 +34,28 @@ __global__ __launch_bounds__(256) void me_gap_kernel(const DevGenomeProblem* __r
   double* out = sprob + P.prob_offset;
   const int total = P.glengthL + P.glengthR;
   for (int e = threadIdx.x; e < total; e += blockDim.x) out[e] = gg_site_prob(P, blocks, nwords, T, e);
+}
+
+// gmapdp_canonical_links: the cross-species stage 2's canonical-link test alone (canon_device.h), one lane per
+// (prevpos, currpos) pair of universal coordinates
+__global__ __launch_bounds__(256) void canon_links_kernel(const uint32_t* __restrict__ blocks, uint64_t nwords,
+                                                          const double* __restrict__ T,
+                                                          const gmapdp_coord_t* __restrict__ prevpos,
+                                                          const gmapdp_coord_t* __restrict__ currpos, long long n,
+                                                          int plusp, gmapdp_coord_t chroffset, uint8_t* __restrict__ out) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    out[i] = canonical_link(blocks, nwords, T, prevpos[i], currpos[i], plusp != 0, chroffset) ? 1 : 0;
+}
+
+hipError_t launch_canon_links(long long n, hipStream_t s, const uint32_t* blocks, uint64_t nwords, const double* T,
+                              const gmapdp_coord_t* prevpos, const gmapdp_coord_t* currpos, int plusp,
+                              gmapdp_coord_t chroffset, gmapdp_coord_t chrhigh, uint8_t* out) {
+  (void)chrhigh;  // (the universal coordinates already carry it; kept beside chroffset as the sweep holds both)
+  if (n <= 0) return hipSuccess;
+  const long long nb = std::min<long long>((n + 255) / 256, 65536);
+  hipLaunchKernelGGL(canon_links_kernel, dim3((unsigned)nb), dim3(256), 0, s, blocks, nwords, T, prevpos, currpos, n,
+                     plusp, chroffset, out);
+  return hipGetLastError();
 }
 
 hipError_t launch_me_sites(long long n, hipStream_t s, const uint32_t* blocks, uint64_t nwords, const double* T,

@@ -2,8 +2,8 @@
 // Stage2_compute (stage2.c:6325) does with the seeding that oi_kernel / oi_map_kernel leave in HBM.
 //
 // Reference semantics restated (paths under the reference tree's src/; GMAP's arguments, gmap.c:1208:
-// localp, skip_repetitive_p, proceed_pctcoverage 0.3, favor_right_p false, max_nalignments 10; no
-// cross-species canonical scoring, no SNPs, STANDARD mode):
+// localp, skip_repetitive_p, proceed_pctcoverage 0.3, favor_right_p false, max_nalignments 10; no SNPs,
+// STANDARD mode; cross-species canonical scoring in the sweep's canonical variant, s2b_canon_kernel):
 //   Diag_update_coverage          diag.c:216
 //   the proceed test              stage2.c:6521-6531
 //   Diag_compute_bounds           diag.c:597 (assign_scores :521, compute_dominance :427,
@@ -31,6 +31,7 @@
 #include <cstdlib>
 
 #include "dp_device.h"
+#include "canon_device.h"
 #include <climits>
 
 namespace gmapdp {
@@ -277,7 +278,18 @@ struct S2E {  // a processed query position: its active hits
   int q, n, start, offq;
   bool inring;
 };
-struct S2W {
+// forms of the range-2 evaluation: s2_eval's one-hit scalar form and its 64-lane chunks, s2_eval1, the
+// one-wave-step windows s2_dloop_fast and s2_dloop_multi
+constexpr int kS2FormScalar = 0, kS2FormChunk = 1, kS2FormEval1 = 2, kS2FormFast = 3, kS2FormMulti = 4;
+// the canonical sweeps' counters since the last gmapdp_debug_canon_counters: [0..4] candidates per form from
+// score_querypos_lookback_one's walk, [5..6] s2_eval's scalar form / chunks called from _mult, [7] shifts
+// whose MaxEnt models were evaluated
+__device__ unsigned long long g_s2_canon[8];
+// kCanon: the cross-species variant of the sweep (GMAPDP_S2_CANONICAL_MIDDLE): range 2 takes
+// NON_CANONICAL_PENALTY_MIDDLE off every link that canonical_link (canon_device.h) declines
+template <bool kC>
+struct S2WT {
+  static constexpr bool kCanon = kC;
   S2Hit* hits;
   const uint32_t* maps;  // chrpos per hit
   int* sc;               // score per hit (fwd_scores)
@@ -287,6 +299,32 @@ struct S2W {
   int *pq, *pn, *poff, *pstart;  // per processed entry: q, active count, off[q], ring start
   int pushed, tracectr, splicingp, lane;
   uint32_t maxintronlen;
+  // kCanon only: the genome, the MaxEnt tables and the call's strand and chromosome
+  const uint32_t* blocks;
+  const double* metab;
+  uint64_t nwords, chroffset, chrhigh;
+  int plusp;
+  // kCanon only: range-2 candidates tested per form of the evaluation (per lane; kS2Form*), shifts whose
+  // MaxEnt models were evaluated; summed into g_s2_canon at the sweep's end (gmapdp_debug_canon_counters)
+  unsigned nform[5], nmult[2], nevals;
+  int in_mult;
+  // the range-2 score of the link from the hit at pp, qd query positions back (fs: without the penalty);
+  // uniform: every lane evaluates the same candidate (counted once)
+  __device__ __forceinline__ int canon(int fs, uint32_t pp, uint32_t position, int qd, int form, bool uniform) {
+    if constexpr (kC) {
+      unsigned ev = 0;
+      if (!canonical_hit_link(blocks, nwords, metab, pp, position, qd, plusp != 0, chroffset, chrhigh, &ev))
+        fs -= kCanonPenaltyMiddle;
+      if (!uniform || lane == 0) {
+        if (in_mult) form = kS2FormMulti + 1 + form;  // (s2_mult only calls s2_eval: forms 0 and 1)
+        if (form < 5) nform[form]++;
+        else if (form == 5) nmult[0]++;
+        else nmult[1]++;
+        nevals += ev;
+      }
+    }
+    return fs;
+  }
 #ifdef GMAPDP_OI_TIMING
   unsigned long long n_cand = 0, n_fast = 0, n_slow = 0, n_multi = 0;  // candidates, fast/multi windows, slow evals
   unsigned long long n_runs = 0, n_runpos = 0, n_onepos = 0, n_multpos = 0;  // runs, their members, other positions
@@ -296,6 +334,7 @@ struct S2W {
 #define S2_TALLY(f, v) (void)0
 #endif
 };
+using S2W = S2WT<false>;
 
 __device__ __forceinline__ S2HV s2_bcast(const S2HV& v, int j) {
   S2HV u;
@@ -324,7 +363,8 @@ __device__ __attribute__((noinline)) S2HV s2_load_global(const S2Hit* hits, cons
   return v;
 }
 
-__device__ __forceinline__ S2HV s2_load(const S2W& W, const S2E& e, int k) {
+template <class SW>
+__device__ __forceinline__ S2HV s2_load(const SW& W, const S2E& e, int k) {
   if (!e.inring) return s2_load_global(W.hits, W.maps, W.sc, W.alist, e.offq, k);  // (callers fence first)
   S2HV v;
   const int s = (e.start + k) & (kS2Ring - 1);
@@ -337,7 +377,8 @@ __device__ __forceinline__ S2HV s2_load(const S2W& W, const S2E& e, int k) {
   return v;
 }
 
-__device__ __forceinline__ S2E s2_mkentry(const S2W& W, int q, int n, int offq, int start) {
+template <class SW>
+__device__ __forceinline__ S2E s2_mkentry(const SW& W, int q, int n, int offq, int start) {
   S2E e;
   e.q = q;
   e.n = n;
@@ -349,7 +390,8 @@ __device__ __forceinline__ S2E s2_mkentry(const S2W& W, int q, int n, int offq, 
 
 // Section A: from active index k_io, the first hit with map + qd >= position (k_io := it, or -1 when
 // the list runs out); true when it sits exactly qd before position (its state in `out`)
-__device__ __forceinline__ bool s2_adj(const S2W& W, const S2E& e, int& k_io, int qd, uint32_t position, S2HV& out) {
+template <class SW>
+__device__ __forceinline__ bool s2_adj(const SW& W, const S2E& e, int& k_io, int qd, uint32_t position, S2HV& out) {
   if (k_io < 0) return false;
   if (e.n == 1 && e.inring) {  // one active hit (the common case): uniform LDS reads, no ballots
     const int sl = e.start & (kS2Ring - 1);
@@ -392,7 +434,8 @@ __device__ __forceinline__ bool s2_adj(const S2W& W, const S2E& e, int& k_io, in
 
 // Ranges 0-4 of score_querypos_lookback_one/_mult against processed entry e from active index start;
 // returns the index where the range-0/1 skipping stopped (the _mult frontier), -1 when the list ran out.
-__device__ __forceinline__ int s2_eval(S2W& W, const S2E& e, int start, int q, uint32_t position, int& last_tr, S2Best& b,
+template <class SW>
+__device__ __forceinline__ int s2_eval(SW& W, const S2E& e, int start, int q, uint32_t position, int& last_tr, S2Best& b,
                        bool range1) {
   const int qd = q - e.q, credit = -qd / kS2K;
   if (e.n == 1 && e.inring && start == 0) {  // one active hit: the ranges in scalar form
@@ -404,7 +447,9 @@ __device__ __forceinline__ int s2_eval(S2W& W, const S2E& e, int start, int q, u
     if (range1 && mp + W.maxintronlen + (uint32_t)qd <= position) return -1;
     if (mp + (uint32_t)kS2EqualNotSplicing + (uint32_t)qd < position) {
       const int diff = (int)(position - mp) - qd;
-      const int fs = s2_u(s2_ring.score[sl]) + credit - (W.splicingp ? (diff / kS2TenThousand + 1) : (diff + 1));
+      const int fs = W.canon(
+          s2_u(s2_ring.score[sl]) + credit - (W.splicingp ? (diff / kS2TenThousand + 1) : (diff + 1)), mp, position, qd,
+          kS2FormScalar, true);
       if (fs > b.score) {
         b.consec = 0;
         b.root = s2_u(s2_ring.root[sl]);
@@ -457,7 +502,8 @@ __device__ __forceinline__ int s2_eval(S2W& W, const S2E& e, int start, int q, u
       int fs = INT_MIN;
       if (in2) {
         const int diff = (int)(position - v.map) - qd;
-        fs = v.score + credit - (W.splicingp ? (diff / kS2TenThousand + 1) : (diff + 1));
+        fs = W.canon(v.score + credit - (W.splicingp ? (diff / kS2TenThousand + 1) : (diff + 1)), v.map, position, qd,
+                     kS2FormChunk, false);
       }
       const int mx = wave_max_i(fs);
       if (m && mx > b.score) {
@@ -500,7 +546,8 @@ __device__ __forceinline__ int s2_eval(S2W& W, const S2E& e, int start, int q, u
 
 // the kk-th newest processed entry (kk < kS2Meta) from the LDS metadata ring
 struct S2EntryCache {
-  __device__ __forceinline__ S2E get(const S2W& W, int np, int kk) {
+  template <class SW>
+  __device__ __forceinline__ S2E get(const SW& W, int np, int kk) {
     const int s = (np - 1 - kk) & (kS2Meta - 1);
     return s2_mkentry(W, s2_u(s2_ring.eq[s]), s2_u(s2_ring.en[s]), s2_u(s2_ring.eoff[s]), s2_u(s2_ring.estart[s]));
   }
@@ -511,7 +558,8 @@ struct S2EntryCache {
 struct S2Pref {
   int q = 0, n = 0, off = 0, start = 0;
   S2HV h = {};
-  __device__ __forceinline__ void load(const S2W& W, int np, int base = 0) {
+  template <class SW>
+  __device__ __forceinline__ void load(const SW& W, int np, int base = 0) {
     const int k = np - 1 - base - W.lane;  // entry base + lane (0: the newest)
     q = n = off = start = 0;
     h = {};
@@ -532,14 +580,16 @@ struct S2Pref {
       }
     }
   }
-  __device__ __forceinline__ S2E entry(const S2W& W, int kk) const {
+  template <class SW>
+  __device__ __forceinline__ S2E entry(const SW& W, int kk) const {
     return s2_mkentry(W, __builtin_amdgcn_readlane(q, kk), __builtin_amdgcn_readlane(n, kk),
                       __builtin_amdgcn_readlane(off, kk), __builtin_amdgcn_readlane(start, kk));
   }
 };
 
 // ranges 0-4 against a processed entry with a single active hit u (scalar); the frontier is 0 or -1
-__device__ __forceinline__ int s2_eval1(S2W& W, int eq, const S2HV& u, int q, uint32_t position, int& last_tr,
+template <class SW>
+__device__ __forceinline__ int s2_eval1(SW& W, int eq, const S2HV& u, int q, uint32_t position, int& last_tr,
                                         S2Best& b, bool range1) {
   const int qd = q - eq;
   if (u.tracei == last_tr) return -1;
@@ -547,7 +597,9 @@ __device__ __forceinline__ int s2_eval1(S2W& W, int eq, const S2HV& u, int q, ui
   if (range1 && u.map + W.maxintronlen + (uint32_t)qd <= position) return -1;
   if (u.map + (uint32_t)kS2EqualNotSplicing + (uint32_t)qd < position) {
     const int diff = (int)(position - u.map) - qd;
-    const int fs = u.score + (-qd / kS2K) - (W.splicingp ? (diff / kS2TenThousand + 1) : (diff + 1));
+    const int fs =
+        W.canon(u.score + (-qd / kS2K) - (W.splicingp ? (diff / kS2TenThousand + 1) : (diff + 1)), u.map, position, qd,
+                kS2FormEval1, true);
     if (fs > b.score) {
       b.consec = 0;
       b.root = u.root;
@@ -573,7 +625,8 @@ __device__ __forceinline__ int s2_eval1(S2W& W, int eq, const S2HV& u, int q, ui
 }
 
 // one processed entry of a lookback: prefetched (kk < 64) or fetched
-__device__ __forceinline__ int s2_entry_eval(S2W& W, const S2Pref& pf, S2EntryCache& ec, int np, int kk, int start,
+template <class SW>
+__device__ __forceinline__ int s2_entry_eval(SW& W, const S2Pref& pf, S2EntryCache& ec, int np, int kk, int start,
                                              int q, uint32_t position, int& last_tr, S2Best& b, bool range1,
                                              int* qd_out) {
   const S2E e = kk < kS2Pref ? pf.entry(W, kk) : ec.get(W, np, kk);
@@ -593,7 +646,8 @@ __device__ __forceinline__ int s2_entry_eval(S2W& W, const S2Pref& pf, S2EntryCa
 // use_f: _mult's per-entry frontiers (lane kk holds f, 0 or -1), updated for the visited entries.
 // Windows past 64 entries: the first 64 here, then (return 2) the walk goes on from entry 64 with
 // last_tr = lt.  Returns 0 (nothing done) when the window holds another kind of entry, 1 when done.
-__device__ __forceinline__ int s2_dloop_fast(S2W& W, const S2Pref& pf, int np, int kmax, int q, uint32_t position,
+template <class SW>
+__device__ __forceinline__ int s2_dloop_fast(SW& W, const S2Pref& pf, int np, int kmax, int q, uint32_t position,
                                              S2Best& b, bool range1, bool use_f, int& f, int& lt) {
   const int kend = kmax < 63 ? kmax : 63;
   const int kk = W.lane;
@@ -616,7 +670,8 @@ __device__ __forceinline__ int s2_dloop_fast(S2W& W, const S2Pref& pf, int np, i
     if (pf.h.map + (uint32_t)kS2EqualNotSplicing + (uint32_t)qd < position) {
       const int diff = (int)(position - pf.h.map) - qd;
       kind = 2;
-      fs = pf.h.score + (-qd / kS2K) - (W.splicingp ? (diff / kS2TenThousand + 1) : (diff + 1));
+      fs = W.canon(pf.h.score + (-qd / kS2K) - (W.splicingp ? (diff / kS2TenThousand + 1) : (diff + 1)), pf.h.map,
+                   position, qd, kS2FormFast, false);
     } else if (pf.h.map + (uint32_t)kS2K <= position) {
       kind = 4;
       fs = pf.h.score + 1;
@@ -676,7 +731,8 @@ __device__ __forceinline__ int s2_dloop_fast(S2W& W, const S2Pref& pf, int np, i
 // number more than 64 the leading entries whose hits fit are taken (a group) and the walk goes on from the
 // next one (return 2, *next = its index, lt = last_tr there).
 // Returns 0 (nothing done) when the window does not fit, else as s2_dloop_fast.
-__device__ __forceinline__ int s2_dloop_multi(S2W& W, const S2Pref& pf, int np, int kmax, int q, uint32_t position,
+template <class SW>
+__device__ __forceinline__ int s2_dloop_multi(SW& W, const S2Pref& pf, int np, int kmax, int q, uint32_t position,
                                               S2Best& b, bool range1, bool use_f, int& f, int& lt, int base = 0,
                                               int* next = nullptr) {
   const int kend = kmax - base < 63 ? kmax - base : 63;
@@ -758,7 +814,8 @@ __device__ __forceinline__ int s2_dloop_multi(S2W& W, const S2Pref& pf, int np, 
     if (v.map + (uint32_t)kS2EqualNotSplicing + (uint32_t)qd < position) {
       const int diff = (int)(position - v.map) - qd;
       kind = 2;
-      fs = v.score + (-qd / kS2K) - (W.splicingp ? (diff / kS2TenThousand + 1) : (diff + 1));
+      fs = W.canon(v.score + (-qd / kS2K) - (W.splicingp ? (diff / kS2TenThousand + 1) : (diff + 1)), v.map, position,
+                   qd, kS2FormMulti, false);
     } else if (v.map + (uint32_t)kS2K <= position) {
       kind = 4;
       fs = v.score + 1;
@@ -814,7 +871,8 @@ __device__ __forceinline__ int s2_dloop_multi(S2W& W, const S2Pref& pf, int np, 
 }
 
 // score_querypos_lookback_one (stage2.c:1073); returns the link
-__device__ __forceinline__ S2Best s2_one(S2W& W, int q, uint32_t position, int np, const S2E& last) {
+template <class SW>
+__device__ __forceinline__ S2Best s2_one(SW& W, int q, uint32_t position, int np, const S2E& last) {
   S2Best b = {kS2K, (int)position, -1, -1, 0, 0};
   int nlookback = kS2Nsufflookback, lookback = kS2Sufflookback;
   S2_SUB_DECL();
@@ -890,7 +948,8 @@ __device__ __forceinline__ S2Best s2_one(S2W& W, int q, uint32_t position, int n
   return b;
 }
 
-__device__ __forceinline__ void s2_store_link(S2W& W, int offq, int hit, const S2Best& b) {
+template <class SW>
+__device__ __forceinline__ void s2_store_link(SW& W, int offq, int hit, const S2Best& b) {
   if (W.lane == 0) {
     W.hits[offq + hit] = S2Hit{b.consec, b.root, b.tracei, b.ph};  // (ph: -1 with pp)
     W.sc[offq + hit] = b.score;
@@ -898,9 +957,11 @@ __device__ __forceinline__ void s2_store_link(S2W& W, int offq, int hit, const S
 }
 
 // score_querypos_lookback_mult (stage2.c:1470) over hits [low, high) of q; links to global
-__device__ __forceinline__ void s2_mult(S2W& W, int q, int offq, int low, int high, int np, const S2E& last) {
+template <class SW>
+__device__ __forceinline__ void s2_mult(SW& W, int q, int offq, int low, int high, int np, const S2E& last) {
   int* fr = s2_fr;
   const int nhits = high - low;
+  if constexpr (SW::kCanon) W.in_mult = 1;
   if (np == 0) {
     for (int i = W.lane; i < nhits; i += 64) {
       W.hits[offq + low + i] = S2Hit{kS2K, (int)W.maps[offq + low + i], W.tracectr + 1 + i, -1};
@@ -961,6 +1022,7 @@ __device__ __forceinline__ void s2_mult(S2W& W, int q, int offq, int low, int hi
     }
     s2_store_link(W, offq, low + i, b);
   }
+  if constexpr (SW::kCanon) W.in_mult = 0;
   wave_sync();
 }
 
@@ -995,7 +1057,8 @@ __device__ __forceinline__ void s2_run_write(S2Hit* hits, int* sc, int* alist, i
 }
 
 // the sweep (stage2.c:3746-4080)
-__device__ __forceinline__ void s2_sweep(S2W& W, const int32_t* npq, int nq, const int* fp, const uint32_t* rmapa,
+template <class SW>
+__device__ __forceinline__ void s2_sweep(SW& W, const int32_t* npq, int nq, const int* fp, const uint32_t* rmapa,
                                          int qstart, int qend) {
   const int lane = W.lane;
   auto npos = [&](int q) { return q < nq ? npq[q] : 0; };
@@ -2080,13 +2143,17 @@ __global__ __launch_bounds__(64) void s2a_kernel(
 #ifndef GMAPDP_S2B_WPE
 #define GMAPDP_S2B_WPE 4  // waves per SIMD the sweep's registers are budgeted for (variants: make variant DEFS=...)
 #endif
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GMAPDP_S2B_WPE))) void s2b_kernel(
+// (the body of both instantiations: s2b_kernel, the default, and s2b_canon_kernel, which also takes the
+// MaxEnt tables)
+template <bool kCanon>
+__device__ __forceinline__ void s2b_body(
     const DevStage2Problem* __restrict__ probs, const uint32_t* __restrict__ blocks, uint64_t nwords,
     const char* __restrict__ qseq, const char* __restrict__ quc, const gmapdp_oligo_result* __restrict__ ores,
     const int32_t* __restrict__ npos_all, const int32_t* __restrict__ map_all, const uint32_t* __restrict__ table_all,
     const int32_t* __restrict__ diag_all, unsigned char* __restrict__ scratch, unsigned long long* __restrict__ counters,
     unsigned long long scratch_cap, gmapdp_stage2_result* __restrict__ results, gmapdp_path* __restrict__ paths_out,
-    unsigned long long path_cap, gmapdp_path_pair* __restrict__ pairs_out, unsigned long long pair_cap) {
+    unsigned long long path_cap, gmapdp_path_pair* __restrict__ pairs_out, unsigned long long pair_cap,
+    const double* __restrict__ metab) {
   __shared__ int sh[8];
   const int lane = threadIdx.x;
   const DevStage2Problem P = probs[s2_problem(counters)];
@@ -2127,7 +2194,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GMAPDP_S2B_W
 #endif
   // ---- align_compute_scores_lookback: the sweep on lane 0 ----
   {
-    S2W W;
+    S2WT<kCanon> W;
+    if constexpr (kCanon) {
+      W.blocks = blocks;
+      W.metab = metab;
+      W.nwords = nwords;
+      W.chroffset = P.chroffset;
+      W.chrhigh = P.chrhigh;
+      W.plusp = P.plusp;
+      for (unsigned& c : W.nform) c = 0;
+      W.nmult[0] = W.nmult[1] = W.nevals = 0;
+      W.in_mult = 0;
+    }
     W.hits = hits;
     W.maps = reinterpret_cast<const uint32_t*>(S + so.maps);
     W.sc = reinterpret_cast<int*>(S + so.sc);
@@ -2145,6 +2223,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GMAPDP_S2B_W
     W.maxintronlen = P.maxintronlen;
     s2_sweep(W, npq, nq, reinterpret_cast<const int*>(S + so.lh), reinterpret_cast<const uint32_t*>(diff), qstart,
              qend);  // q0's range / rmap (s2a_kernel)
+    if constexpr (kCanon) {
+      for (int f = 0; f < 8; f++) {
+        const unsigned mine = f < 5 ? W.nform[f] : f < 7 ? W.nmult[f - 5] : W.nevals;
+        const int all = wave_sum_i((int)mine);
+        if (lane == 0 && all) atomicAdd(&g_s2_canon[f], (unsigned long long)all);
+      }
+    }
   }
   wave_sync();
 #ifdef GMAPDP_OI_TIMING
@@ -2156,6 +2241,35 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GMAPDP_S2B_W
 #endif
 
   S2_MARK(4);
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GMAPDP_S2B_WPE))) void s2b_kernel(
+    const DevStage2Problem* __restrict__ probs, const uint32_t* __restrict__ blocks, uint64_t nwords,
+    const char* __restrict__ qseq, const char* __restrict__ quc, const gmapdp_oligo_result* __restrict__ ores,
+    const int32_t* __restrict__ npos_all, const int32_t* __restrict__ map_all, const uint32_t* __restrict__ table_all,
+    const int32_t* __restrict__ diag_all, unsigned char* __restrict__ scratch, unsigned long long* __restrict__ counters,
+    unsigned long long scratch_cap, gmapdp_stage2_result* __restrict__ results, gmapdp_path* __restrict__ paths_out,
+    unsigned long long path_cap, gmapdp_path_pair* __restrict__ pairs_out, unsigned long long pair_cap) {
+  s2b_body<false>(probs, blocks, nwords, qseq, quc, ores, npos_all, map_all, table_all, diag_all, scratch, counters,
+                  scratch_cap, results, paths_out, path_cap, pairs_out, pair_cap, nullptr);
+}
+
+// the cross-species sweep (GMAPDP_S2_CANONICAL_MIDDLE): the same arguments, then the MaxEnt tables
+// (budgeted for 2 waves per SIMD: 178 VGPRs without scratch; at 3 and 4 the predicate's windows and the FP64
+// products spill, 16 and 112 bytes per lane)
+#ifndef GMAPDP_S2B_CANON_WPE
+#define GMAPDP_S2B_CANON_WPE 2
+#endif
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GMAPDP_S2B_CANON_WPE))) void s2b_canon_kernel(
+    const DevStage2Problem* __restrict__ probs, const uint32_t* __restrict__ blocks, uint64_t nwords,
+    const char* __restrict__ qseq, const char* __restrict__ quc, const gmapdp_oligo_result* __restrict__ ores,
+    const int32_t* __restrict__ npos_all, const int32_t* __restrict__ map_all, const uint32_t* __restrict__ table_all,
+    const int32_t* __restrict__ diag_all, unsigned char* __restrict__ scratch, unsigned long long* __restrict__ counters,
+    unsigned long long scratch_cap, gmapdp_stage2_result* __restrict__ results, gmapdp_path* __restrict__ paths_out,
+    unsigned long long path_cap, gmapdp_path_pair* __restrict__ pairs_out, unsigned long long pair_cap,
+    const double* __restrict__ metab) {
+  s2b_body<true>(probs, blocks, nwords, qseq, quc, ores, npos_all, map_all, table_all, diag_all, scratch, counters,
+                 scratch_cap, results, paths_out, path_cap, pairs_out, pair_cap, metab);
 }
 
 // traceback_one over the LDS link table, 8 B per hit: lql[i] = query position << 16 | a bit 15 set when
@@ -2728,6 +2842,13 @@ extern "C" int gmapdp_debug_s2_marks(unsigned long long* out) {
 }
 #endif
 
+// the canonical sweeps' counters (g_s2_canon) since the last call, then cleared; the device must be idle
+int s2_canon_counters(unsigned long long* out8) {
+  if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_s2_canon), sizeof(g_s2_canon)) != hipSuccess) return 1;
+  static const unsigned long long zero[8] = {};
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_s2_canon), zero, sizeof(zero)) != hipSuccess;
+}
+
 size_t scratch_bytes_s2c(int querylength, int totalpositions, int ndiagonals) {
   return s2_scratch(querylength, totalpositions, ndiagonals).total;
 }
@@ -2737,11 +2858,13 @@ hipError_t launch_s2c(int nproblems, hipStream_t stream, const DevStage2Problem*
                       const int32_t* npos, const int32_t* map, const uint32_t* table, const int32_t* diags,
                       unsigned char* scratch, unsigned long long* counters, unsigned long long scratch_cap,
                       gmapdp_stage2_result* results, gmapdp_path* paths, unsigned long long path_cap,
-                      gmapdp_path_pair* pairs, unsigned long long pair_cap, bool modal, int phases) {
+                      gmapdp_path_pair* pairs, unsigned long long pair_cap, bool modal, int phases,
+                      const double* canon_metab) {
+  // canon_metab: the MaxEnt tables of a GMAPDP_S2_CANONICAL_MIDDLE batch (the sweep's canonical variant), else NULL
   void* args[] = {(void*)&probs, (void*)&blocks, (void*)&nwords, (void*)&qseq, (void*)&quc, (void*)&ores,
                   (void*)&npos, (void*)&map, (void*)&table, (void*)&diags, (void*)&scratch, (void*)&counters,
                   (void*)&scratch_cap, (void*)&results, (void*)&paths, (void*)&path_cap, (void*)&pairs,
-                  (void*)&pair_cap};
+                  (void*)&pair_cap, (void*)&canon_metab};
   // phases (bits): 1 the order + s2a, 2 s2b, 4 s2c; one phase alone re-runs it over the previous run's
   // scratch (the bench's per-kernel timing)
   hipError_t e = hipSuccess;
@@ -2764,11 +2887,9 @@ hipError_t launch_s2c(int nproblems, hipStream_t stream, const DevStage2Problem*
       const char* v = std::getenv("GMAPDP_S2B_LDS");
       return v ? (size_t)std::strtoull(v, nullptr, 10) : (size_t)0;
     }();
-    if (xlds > 64 * 1024)
-      e = hipFuncSetAttribute(reinterpret_cast<void*>(&s2b_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)xlds);
-    if (e == hipSuccess)
-      e = hipLaunchKernel(reinterpret_cast<void*>(&s2b_kernel), dim3(nproblems), dim3(64), args, xlds, stream);
+    void* sweep = canon_metab ? reinterpret_cast<void*>(&s2b_canon_kernel) : reinterpret_cast<void*>(&s2b_kernel);
+    if (xlds > 64 * 1024) e = hipFuncSetAttribute(sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds);
+    if (e == hipSuccess) e = hipLaunchKernel(sweep, dim3(nproblems), dim3(64), args, xlds, stream);
   }
   if (e == hipSuccess && (phases & 4)) {  // the heavy calls (first in the order) without LDS, then the rest
     // (modal: a cmet / atoi / ttoc context's pair emission, convert_to_nucleotides outside STANDARD)

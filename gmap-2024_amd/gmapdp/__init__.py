@@ -114,7 +114,10 @@ class ScanResult(C.Structure):
 class Stage2Problem(C.Structure):
     _fields_ = [("qoff", C.c_int32), ("querylength", C.c_int32), ("chrstart", C.c_uint32), ("chrend", C.c_uint32),
                 ("chroffset", C.c_uint64), ("chrhigh", C.c_uint64), ("plusp", C.c_int32), ("splicingp", C.c_int32),
-                ("maxintronlen", C.c_int32), ("pad_", C.c_int32)]
+                ("maxintronlen", C.c_int32), ("flags", C.c_int32)]
+
+
+S2_CANONICAL_MIDDLE = 1  # GMAPDP_S2_CANONICAL_MIDDLE: gmap --cross-species
 
 
 class Stage2Result(C.Structure):
@@ -322,6 +325,9 @@ def load_library(path=LIB_PATH):
         "gmapdp_expand_path_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                                C.c_int]),
         "gmapdp_maxent_sites": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+        "gmapdp_debug_canon_counters": (C.c_int, [C.c_void_p, C.c_void_p]),
+        "gmapdp_canonical_links": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint64,
+                                             C.c_uint64, C.c_void_p]),
         "gmapdp_microexon_plan_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                    C.c_size_t, P(C.c_void_p)]),
         "gmapdp_microexon_plan_candidates": (C.c_size_t, [C.c_void_p]),
@@ -601,6 +607,26 @@ class Engine:
                                                  out.ctypes.data), "gmapdp_maxent_sites")
         return out
 
+    def canonical_links(self, prevpos, currpos, plusp, chroffset, chrhigh):
+        """The cross-species stage 2's canonical-link test (stage2.c:1257-1312) per (prevpos, currpos) pair of
+        universal coordinates on the device: a uint8 array, 1 canonical (gmapdp_canonical_links)."""
+        pp = np.ascontiguousarray(prevpos, dtype=np.uint64)
+        cp = np.ascontiguousarray(currpos, dtype=np.uint64)
+        if pp.shape != cp.shape:
+            raise ValueError("prevpos and currpos differ in length")
+        out = np.zeros(len(pp), dtype=np.uint8)
+        self._check(self.lib.gmapdp_canonical_links(self.h, pp.ctypes.data, cp.ctypes.data, len(pp), int(bool(plusp)),
+                                                    int(chroffset), int(chrhigh), out.ctypes.data),
+                    "gmapdp_canonical_links")
+        return out
+
+    def canon_counters(self):
+        """gmapdp_debug_canon_counters: 8 counts of the cross-species sweeps since the last call (range-2
+        candidates by form of the evaluation, [7] MaxEnt-evaluated shifts); clears them."""
+        out = np.zeros(8, dtype=np.uint64)
+        self._check(self.lib.gmapdp_debug_canon_counters(self.h, out.ctypes.data), "gmapdp_debug_canon_counters")
+        return [int(x) for x in out]
+
     # -- batched Dynprog_genome_gap -------------------------------------------
     def genome_gap_batch_raw(self, probs, qbuf, qucbuf, splice_probs):
         """splice_probs: the probability arena, or DEVICE (the engine's device MaxEnt: a NULL arena)."""
@@ -809,9 +835,9 @@ class Engine:
 
     # -- batched Stage2_compute (seeding + chaining) -----------------------------------------------
     @staticmethod
-    def build_stage2_batch(calls):
+    def build_stage2_batch(calls, cross_species=False):
         """calls: dicts (q, quc, chrstart, chrend, chroffset, chrhigh, plusp, splicingp, maxintronlen)
-        -> (problems, qbuf, qucbuf)."""
+        -> (problems, qbuf, qucbuf).  cross_species: every call carries GMAPDP_S2_CANONICAL_MIDDLE."""
         calls = list(calls)
         probs = np.zeros(len(calls), dtype=STAGE2_PROBLEM_DTYPE)
         qs, qus, off = [], [], 0
@@ -822,6 +848,7 @@ class Engine:
                 probs[i][k] = int(p.get(k, 0))
             probs[i]["splicingp"] = int(p.get("splicingp", 1))
             probs[i]["maxintronlen"] = int(p.get("maxintronlen", 500000))
+            probs[i]["flags"] = S2_CANONICAL_MIDDLE if cross_species else 0
             qs.append(p.get("q", p["quc"]))
             qus.append(p["quc"])
             off += len(p["quc"])
@@ -844,10 +871,11 @@ class Engine:
             self._check(rc, "gmapdp_stage2_batch")
             return results, paths[:pn.value], pairs[:qn.value]
 
-    def stage2_batch(self, calls):
-        """Per call (number of results, [pair-key list per result]) -- the oracle's format (dpbind)."""
+    def stage2_batch(self, calls, cross_species=False):
+        """Per call (number of results, [pair-key list per result]) -- the oracle's format (dpbind).
+        cross_species: gmap --cross-species (GMAPDP_S2_CANONICAL_MIDDLE)."""
         calls = list(calls)
-        probs, qbuf, qucbuf = self.build_stage2_batch(calls)
+        probs, qbuf, qucbuf = self.build_stage2_batch(calls, cross_species)
         results, paths, pairs = self.stage2_batch_raw(probs, qbuf, qucbuf)
         out = []
         for r in results:
@@ -865,7 +893,8 @@ class Engine:
             out.append((int(r["nresults"]), lists))
         return out
 
-    def stage2_plan_raw(self, probs, qbuf, qucbuf, run_qbuf=None, run_qucbuf=None, compact_out=None):
+    def stage2_plan_raw(self, probs, qbuf, qucbuf, run_qbuf=None, run_qucbuf=None, compact_out=None,
+                        cross_species=False, whats=(3,), reruns=0):
         """The device-resident Stage2_compute plan (bench.py's path): gmapdp_stage2_plan_create on
         (probs, qbuf, qucbuf) -- its sizing run, the measured re-layout, the 16-bit seeding class --,
         gmapdp_stage2_plan_run(what = 3) against device copies of the query arenas (run_qbuf /
@@ -873,8 +902,13 @@ class Engine:
         (results, paths, pairs, (calls with 16-bit, with 32-bit seeding counters)).  compact_out (a dict):
         also the compact stream of the path pairs (gmapdp_stage2_plan_compact_pairs) expanded on the host
         (gmapdp_expand_path_pairs): compact_out["pairs"] (an arena like `pairs`), ["bytes"], ["bound"]
-        (gmapdp_stage2_plan_compact_bound)."""
+        (gmapdp_stage2_plan_compact_bound).  cross_species: the plan's calls carry GMAPDP_S2_CANONICAL_MIDDLE
+        (probs is not modified).  whats: the `what` values of the run, in order ((3,) or (1, 4, 8, 16));
+        reruns: how many more times the same run is made before the fetch."""
         lib, n = self.lib, len(probs)
+        if cross_species:
+            probs = probs.copy()
+            probs["flags"] = S2_CANONICAL_MIDDLE
         hip = _hip()
         plan = C.c_void_p()
         self._check(lib.gmapdp_stage2_plan_create(self.h, probs.ctypes.data, n, qbuf, qucbuf, len(qucbuf),
@@ -898,7 +932,10 @@ class Engine:
             assert len(rq) == len(qbuf) and len(rqu) == len(qucbuf)
             d_q, d_quc = dbuf(len(rq), rq), dbuf(len(rqu), rqu)
             d_res = dbuf(n * STAGE2_RESULT_DTYPE.itemsize)
-            self._check(lib.gmapdp_stage2_plan_run(self.h, plan, d_q, d_quc, d_res, 3, None), "gmapdp_stage2_plan_run")
+            for _ in range(1 + reruns):
+                for what in whats:
+                    self._check(lib.gmapdp_stage2_plan_run(self.h, plan, d_q, d_quc, d_res, what, None),
+                                "gmapdp_stage2_plan_run")
             results = np.zeros(n, dtype=STAGE2_RESULT_DTYPE)
             pn, qn = C.c_size_t(), C.c_size_t()
             rc = lib.gmapdp_stage2_plan_fetch(self.h, plan, d_res, None, results.ctypes.data, None, 0, None, 0,

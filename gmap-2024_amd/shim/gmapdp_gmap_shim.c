@@ -127,6 +127,7 @@ static const char *const shim_stat_name[ST_N] = {"Dynprog_single_gap", "Dynprog_
                                                  "Dynprog_end3_splicejunction", "Dynprog_end5_known",
                                                  "Dynprog_end3_known"};
 static unsigned long shim_stats[ST_N];
+static unsigned long shim_cross_species;  /* Stage2_compute calls sent with GMAPDP_S2_CANONICAL_MIDDLE */
 
 static unsigned long shim_batches, shim_batched;
 static FILE *shim_trace = NULL;  /* GMAPDP_SHIM_TRACE: per-batch record (diagnostics) */
@@ -145,6 +146,7 @@ shim_print_stats (void) {
   int i;
   fprintf(stderr, "gmapdp shim calls:");
   for (i = 0; i < ST_N; i++) fprintf(stderr, " %s=%lu", shim_stat_name[i], __atomic_load_n(&shim_stats[i], __ATOMIC_RELAXED));
+  fprintf(stderr, " Stage2_compute_cross_species=%lu", __atomic_load_n(&shim_cross_species, __ATOMIC_RELAXED));
   fprintf(stderr, " batches=%lu mean_batch=%.2f dp_s=%.3f cdna_s=%.3f stage2_s=%.3f chain_s=%.3f\n", shim_batches,
           shim_batches ? (double) shim_batched / (double) shim_batches : 0.0, shim_secs[0], shim_secs[1], shim_secs[2],
           shim_secs[3]);
@@ -2425,7 +2427,8 @@ __wrap_Oligoindex_get_mappings (List_T diagonals, bool *coveredp, Chrpos_T **map
 /* ---- Stage2_compute (stage2.c:6325): seeding + chaining on the engine ----
    gmap.c's calls (update_stage3middle_list / update_stage3list, gmap.c:1208 / 1323) pass the major
    oligoindex array, localp, skip_repetitive_p, favor_right_p false and max_nalignments 10; the engine
-   restates exactly that configuration and the shim refuses any other.  Each returned Stage2_T holds
+   restates exactly that configuration and the shim refuses any other.  Stage2_setup's cross_species_p
+   (gmap --cross-species) travels as GMAPDP_S2_CANONICAL_MIDDLE.  Each returned Stage2_T holds
    the middle path's pairs, pushed into the caller's Pairpool in list order; its all_starts / all_ends
    stay NULL as in the reference (MOVE_TO_STAGE3 undefined). */
 extern void __real_Stage2_setup (bool splicingp_in, bool cross_species_p, int suboptimal_score_start_in,
@@ -2476,7 +2479,6 @@ __wrap_Stage2_compute (char *queryseq_ptr, char *queryuc_ptr, int querylength, i
   (void) genestrand;
   if (s2_mode != shim_mode) shim_refuse("Stage2_setup and Dynprog_init given different modes");
   shim_refuse_stage2_mode("Stage2_compute");
-  if (s2_cross_species_p) shim_refuse("Stage2_compute with cross-species canonical scoring");
   if (s2_snps_p || (genomealt != NULL && genomealt != genome)) shim_refuse("Stage2_compute with an SNP genome");
   if (s2_sufflookback != 60 || s2_nsufflookback != 5) shim_refuse("Stage2_compute with non-default lookback");
   if (diag_debug) shim_refuse("Stage2_compute diagnostics (diag_debug)");
@@ -2525,6 +2527,8 @@ __wrap_Stage2_compute (char *queryseq_ptr, char *queryuc_ptr, int querylength, i
   p->plusp = plusp ? 1 : 0;
   p->splicingp = s2_splicingp;
   p->maxintronlen = s2_maxintronlen;
+  /* gmap --cross-species (Stage2_setup is called once, so every call of a batch carries the same flags) */
+  p->flags = s2_cross_species_p ? GMAPDP_S2_CANONICAL_MIDDLE : 0;
   r->genome = genome;
   r->q = queryseq_ptr;
   r->quc = queryuc_ptr;
@@ -2540,6 +2544,7 @@ __wrap_Stage2_compute (char *queryseq_ptr, char *queryuc_ptr, int querylength, i
   }
   shim_submit(r);
   shim_count(ST_STAGE2);
+  if (s2_cross_species_p) __atomic_fetch_add(&shim_cross_species, 1UL, __ATOMIC_RELAXED);
   /* the results in list order: build from the last (each List_push prepends) */
   for (k = r->s2r.nresults - 1; k >= 0; k--) {
     const gmapdp_path *pa = &r->s2paths[k];

@@ -281,6 +281,22 @@ int gmapdp_maxent_available (char *path, size_t path_bytes);
 int gmapdp_maxent_sites (gmapdp_ctx *ctx, const gmapdp_coord_t *positions, const uint8_t *models,
                          const gmapdp_coord_t *chroffsets, size_t n, double *out);
 
+/* Diagnostic: out[i] = 1 when the cross-species stage 2 (GMAPDP_S2_CANONICAL_MIDDLE) finds the link between
+ * the seed ends prevpos[i] and currpos[i] canonical, else 0 -- the decision of stage2.c:1257-1312 alone, on
+ * the universal coordinates it computes there (plus strand: prevpos < currpos; minus: currpos < prevpos),
+ * over ctx's genome with chroffset as the MaxEnt calls' chromosome offset (synchronous).  chrhigh is the
+ * sweep's other chromosome bound; the coordinates given already carry it. */
+int gmapdp_canonical_links (gmapdp_ctx *ctx, const gmapdp_coord_t *prevpos, const gmapdp_coord_t *currpos, size_t n,
+                            int plusp, gmapdp_coord_t chroffset, gmapdp_coord_t chrhigh, uint8_t *out);
+
+/* Test / measurement aid: what the cross-species sweeps of ctx's device did since the last call (then cleared;
+ * synchronises the device).  out8[0..4]: range-2 candidates tested in the walk of
+ * score_querypos_lookback_one, by form of the evaluation -- the one-hit scalar form, the 64-lane chunks, the
+ * prefetched one-hit form, the one-step window of one-hit entries, the one-step window of entries with several
+ * hits; out8[5..6]: candidates tested from score_querypos_lookback_mult, scalar form and chunks; out8[7]: shifts
+ * at which both dinucleotides matched and the two MaxEnt models were evaluated. */
+int gmapdp_debug_canon_counters (gmapdp_ctx *ctx, unsigned long long *out8);
+
 /* For each problem, write glengthL + glengthR (splicesitepos, model) pairs
  * at the problem's prob_offset: the arguments of the Maxent_hr_*_prob call
  * (with the problem's chroffset) whose result belongs at that entry
@@ -641,8 +657,8 @@ void gmapdp_scan_plan_destroy (gmapdp_scan_plan *plan);
 /* Stage2_compute (stage2.c:6325) as GMAP's update_stage3middle_list calls it (gmap.c:1208-1215):
  * query_offset 0, genestrand 0, proceed_pctcoverage 0.3, the major oligoindex array (8-mers,
  * diag_lookback 120, suffnconsecutive 20), localp, skip_repetitive_p, favor_right_p false,
- * max_nalignments 10; Stage2_setup (gmap.c:6544) without cross-species canonical scoring, without SNPs,
- * the context's mode (STANDARD or a stranded cmet / atoi / ttoc mode, see gmapdp_oligo_problem: there the
+ * max_nalignments 10; Stage2_setup (gmap.c:6544) without SNPs, cross-species canonical scoring
+ * (gmap --cross-species) by `flags`, the context's mode (STANDARD or a stranded cmet / atoi / ttoc mode, see gmapdp_oligo_problem: there the
  * pairs' genome characters are the real genome's and comp is ':' where the query character differs,
  * convert_to_nucleotides stage2.c:5403-5452), sufflookback 60, nsufflookback 5.  queryseq_ptr = qseq + qoff
  * (case as given, the Pair cdna), queryuc_ptr = qseq_uc + qoff.  Domain as for gmapdp_oligo_problem: querylength > 8, and
@@ -657,8 +673,21 @@ typedef struct {
   int32_t plusp;
   int32_t splicingp;       /* Stage2_setup's splicingp_in (novelsplicingp || knownsplicingp) */
   int32_t maxintronlen;    /* Stage2_setup's maxintronlen_in */
-  int32_t pad_;
+  int32_t flags;           /* GMAPDP_S2_* bits; 0: GMAP's default.  One value per batch or plan */
 } gmapdp_stage2_problem;
+
+/* gmapdp_stage2_problem.flags.  GMAPDP_S2_CANONICAL_MIDDLE: Stage2_setup's cross_species_p
+ * (use_canonical_middle_p, stage2.c:139-143).  Range 2 of score_querypos_lookback_one / _mult
+ * (stage2.c:1252-1321 / 1816-1881) then takes NON_CANONICAL_PENALTY_MIDDLE (4) off every candidate link
+ * across a genomic skip unless Genome_sense_canonicalp or Genome_antisense_canonicalp
+ * (genome_canonical.c:361 / 466) finds a GT..AG (CT..AC) pair at one shift in the two 23-nt windows
+ * around the seed ends with both MaxEnt probabilities above 0.9 -- evaluated on the device over the
+ * context's genome (genomealt == genome) with the device MaxEnt tables, in every stage-2 entry point
+ * (gmapdp_stage2_batch, gmapdp_stage2_plan_create / _run / _fetch, the compact stream).  All calls of one
+ * batch or plan carry the same flags: a mix, or a bit not listed here, is GMAPDP_EINVAL.  Without the
+ * MaxEnt tables the flag fails with GMAPDP_EINVAL ("maxent tables: ..."), as device MaxEnt does for genome
+ * gaps. */
+#define GMAPDP_S2_CANONICAL_MIDDLE 1
 
 /* Per call: the returned List_T of Stage2_T, in list order, as nresults path records starting at
  * paths[path_offset]; each record's pairs are its Stage2_middle list (all_starts / all_ends are NULL

@@ -39,6 +39,8 @@ def main():
     ap.add_argument("--cpu-configs", default="cpu:",
                     help="environment configurations for the unmodified program's runs, same syntax (e.g. the same "
                          "malloc tunables as a GPU configuration, for a like-for-like comparison)")
+    ap.add_argument("--gmap-args", default="",
+                    help="extra gmap arguments for both programs, space-separated (e.g. --gmap-args=--cross-species)")
     ap.add_argument("--skip-cpu", action="store_true")
     ap.add_argument("--thread-cpu", action="store_true", help="per-thread-name CPU seconds of each run")
     ap.add_argument("--prof", default=None,
@@ -68,7 +70,7 @@ def main():
         M.write_fasta(os.path.join(tmp, "r.fa"), reads)
         gargs = ["-g", "g.fa"]
     ref = os.path.join(ROOT, "oracle", "_ref")
-    out = {"reads": a.reads, "build": a.build, "mode": "-d %s" % meta["name"] if a.index else "-g", "cpu_model": None,
+    out = {"reads": a.reads, "build": a.build, "gmap_args": a.gmap_args, "mode": "-d %s" % meta["name"] if a.index else "-g", "cpu_model": None,
            "runs": []}
     try:
         out["cpu_model"] = next(l.split(":", 1)[1].strip() for l in open("/proc/cpuinfo") if l.startswith("model name"))
@@ -101,7 +103,8 @@ def main():
                 os.makedirs(a.prof, exist_ok=True)
                 env["PCPROF_OUT"] = os.path.abspath(os.path.join(a.prof, "pcprof_%s_%s_t%d.txt" % (prog, cname, t)))
                 profs.append(env["PCPROF_OUT"])
-            args = [os.path.join(ref, prog), "-t", str(t), "-O"] + gargs + ["-f", "samse", "--no-sam-headers", "r.fa"]
+            args = ([os.path.join(ref, prog), "-t", str(t), "-O"] + a.gmap_args.split() + gargs +
+                    ["-f", "samse", "--no-sam-headers", "r.fa"])
             t0 = time.perf_counter()
             ru0 = resource.getrusage(resource.RUSAGE_CHILDREN)
             threads = None
