@@ -157,7 +157,8 @@ __host__ __device__ inline Carve carve_dp(int rlength, int glength, int R, bool 
 }
 
 // direction planes: [c][t][i] 64-bit masks; t: 0 nogap=HORIZ, 1 nogap=VERT, 2 Egap=HORIZ, 3 Fgap=VERT;
-// band offset k lives in word i = k % R at bit k / R.
+// band offset k lives in word i = k % R at bit k / R.  Plane 3 is stored one row up: the word's bit for
+// offset k is the Fgap direction of the cell below, offset k + 1 (BandDirs / PackedDirs undo the shift).
 // bitoff: first bit of the problem's segment when a packed wave stores whole-wave ballots
 template <int R, typename WORD = uint64_t>
 __device__ __forceinline__ uint32_t dir_bit(const WORD* dirs, int c, int t, int k, int W, int bitoff = 0) {
@@ -360,8 +361,9 @@ struct PackedDirs {
   const uint32_t* hi;
   int W, uband, nhigh;
   __device__ uint32_t operator()(int c, int t, int r) const {
-    const int k = r - c + uband;
+    int k = r - c + uband;
     if (k < 0 || k >= W) return 0u;  // outside the band: cleared to DIAG (dynprog.c:498)
+    if (t == 3 && --k < 0) return 0u;  // Fgap of (r, c) is stored with the cell above it (fill_band)
     if (k < 32) return (lo[4 * c + t] >> k) & 1u;
     const int b = t * 8 * nhigh + (k - 32);
     return (hi[c * nhigh + (b >> 5)] >> (b & 31)) & 1u;
@@ -494,26 +496,16 @@ __device__ __forceinline__ void fill_band(int lane, int rlen, int glen, int lban
       vb[i] = F[i] > Hp[i] - late;
       Hun[i] = max(F[i], Hp[i]);
     }
-    // Fgap direction needs F(r-1), H(r-1) of this column (dynprog.c:1486-1492).  Lane 0's element 0 reads
-    // them only when valid, and then it is the column's top row (r = rtop = rlo), which takes the constants
-    // below instead: a whole-wave fill shifts in zeros there (one DPP move, no default copied in first).
-    int Fup, Hup;
-    if constexpr (S == 64) {
-      Fup = dpp_wave_shr1_zero(F[R - 1]);
-      Hup = dpp_wave_shr1_zero(Hun[R - 1]);
-    } else {
-      Fup = seg_shr1<S>(F[R - 1], kNegInf32, lk);
-      Hup = seg_shr1<S>(Hun[R - 1], kNegInf32, lk);
-    }
+    // Fgap direction of cell (r, c) is F(r-1, c) > H(r-1, c) + open - late (dynprog.c:1486-1492): a property
+    // of the cell above alone.  Each cell forms the bit of the cell below it from its own registers, stored
+    // at its own band offset, and the readers take plane 3 of (r, c) at offset k - 1 of the column (0 at
+    // k = 0 and, through the valid mask, at the column's first valid row).
     uint64_t mH[R], mV[R], mE[R], mF[R];
 #pragma unroll
     for (int i = 0; i < R; i++) {
       const int k = lk * R + i;
       const int r = rtop + k;
-      const bool top = r == rlo;
-      const int fprev = top ? kNegInf32 : ((i == 0) ? Fup : F[i - 1]);
-      const int hprev = top ? L0 : ((i == 0) ? Hup : Hun[i - 1]);
-      const bool fb = fprev > hprev + open - late;
+      const bool fb = F[i] > Hun[i] + open - late;
       const uint64_t mvalid = ballot(valid[i]);
       mV[i] = ballot(vb[i]) & mvalid;
       mH[i] = ballot(hb[i]) & ~mV[i] & mvalid;
@@ -868,7 +860,10 @@ struct BandDirs {
   const WORD* dirs;
   int W, uband, bitoff;
   __device__ uint32_t operator()(int c, int t, int r) const {
-    return dir_bit<R, WORD>(dirs, c, t, r - c + uband, W, bitoff);
+    const int k = r - c + uband;
+    // Fgap of cell (r, c) is stored with cell (r-1, c), band offset k - 1 (fill_band); nothing above offset 0
+    if (t == 3) return k < W ? dir_bit<R, WORD>(dirs, c, t, k - 1, W, bitoff) : 0u;
+    return dir_bit<R, WORD>(dirs, c, t, k, W, bitoff);
   }
 };
 
@@ -1220,9 +1215,9 @@ __device__ inline bool gg_simple_wave(int lane, const DevGenomeProblem& P, int p
   res.introntype = it;
   const int finalscore = halfp ? bestscore - scoreI / 2 : bestscore;
   if (finalscore <= 0) return false;
-  if (ks) {
-    res.left_prob = ks[bestrL] ? 1.0 : raw ? raw[bestrL] : gg_site_prob(P, blocks, nwords, metab, bestrL);
-    res.right_prob = ks[rlen + 1 + bestrR] ? 1.0
+  if (ks || !pL) {  // (pL NULL: no staged probabilities, the two sites are evaluated on demand)
+    res.left_prob = (ks && ks[bestrL]) ? 1.0 : raw ? raw[bestrL] : gg_site_prob(P, blocks, nwords, metab, bestrL);
+    res.right_prob = (ks && ks[rlen + 1 + bestrR]) ? 1.0
                    : raw ? raw[P.glengthL + bestrR] : gg_site_prob(P, blocks, nwords, metab, P.glengthL + bestrR);
   } else {
     res.left_prob = pL[bestrL];

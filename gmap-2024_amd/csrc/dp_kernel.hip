@@ -699,7 +699,8 @@ __host__ __device__ inline ScratchGG scratch_gg(int rlength, int glengthL, int g
 }
 
 // GMAPDP_GGX_*: timing experiments only (make variant; outputs are garbage): NOSTAGE stages constants
-// instead of loading, NOEMIT ends after the fills, WPE sets amdgpu_waves_per_eu.
+// instead of loading, NOME stages the probabilities without evaluating the MaxEnt models, NOEMIT ends after
+// the fills, WPE sets amdgpu_waves_per_eu.
 #ifdef GMAPDP_GGX_WPE
 #define GGX_ATTR __attribute__((amdgpu_waves_per_eu(GMAPDP_GGX_WPE)))
 #else
@@ -762,8 +763,99 @@ __global__ __launch_bounds__(128) GGX_ATTR void gg_kernel(
   const bool kn = flags & kGKnown;  // known splice sites (get_known_splicesites, dynprog_genome.c:405)
   const uint8_t* kb = kn ? known + P.known_offset : nullptr;
 
-  // ---- stage (both waves): per query row the 4-bit score word in both DP orders, both genome
-  //      segments as classes, dinucleotide codes, the splice probabilities, the intron scores ----
+  // ---- stage: per query row the 4-bit score word in both DP orders, both genome segments as classes,
+  //      dinucleotide codes, the splice probabilities, the intron scores.  An unflagged problem stages all of
+  //      it in one pass of both waves.  A problem flagged for genome_gap_simple stages first only what
+  //      gg_simple_wave reads (classes, dinucleotide codes, intron scores): the simple test takes its two
+  //      probabilities on demand, and most flagged problems end there.  The score words and the
+  //      probabilities (MaxEnt at every position of both segments) follow on wave 1 while wave 0 runs the
+  //      test: off the answered gaps' issue path on wave 0, ready sooner for the declined ones than when
+  //      both waves stage them after the test (GMAPDP_GG_PROBS_AFTER_DECLINE, measured slower) ----
+  const bool lazy = flags & kGSimple;
+  // score words, rows t0, t0 + nt, ...
+  auto stage_scores = [&](int t0, int nt) __attribute__((always_inline)) {
+    for (int i = t0; i < rlen; i += nt) {
+      const char c1 = qseq[P.qbase + i];
+      const uint64_t row = *reinterpret_cast<const uint64_t*>(sct + (uint8_t)(c1 & 127) * kNClass);
+      uint32_t w = 0;
+#pragma unroll
+      for (int g = 0; g < 6; g++) w |= (uint32_t)((row >> (8 * g)) & 0xfu) << (4 * g);
+      scL[i + 1] = (int32_t)w;
+      scR[rlen - i] = (int32_t)w;
+    }
+    if (t0 < 2) {
+      scL[t0 ? rlen + 1 : 0] = 0;
+      scR[t0 ? rlen + 1 : 0] = 0;
+    }
+  };
+  // Both segments as one index space jj (L: i = jj, R: i = jj - gL), two items per thread per pass with
+  // every load issued before any is used: segment_nt's bounds (Genome_get_segment_right/left) become a
+  // class or a block address, then the flags word and the half word of each block are loaded together.
+  // CLS: the classes; PRB: the splice probabilities; items t0, t0 + nt, ...
+  auto stage_segments = [&](const bool CLS, const bool PRB, int t0, int nt) __attribute__((always_inline)) {
+    const int nG = gL + gR;
+    for (int b0 = t0; b0 < nG; b0 += 2 * nt) {
+      uint32_t wf[2] = {0, 0}, wv[2] = {0, 0}, bit[2] = {0, 0};
+      int cls[2] = {0, 0};  // kStar / kN decided from the bounds, -1: decode the words
+      double pv[2] = {0.0, 0.0};
+      bool rcv[2] = {false, false};
+#pragma unroll
+      for (int u = 0; u < 2; u++) {
+        const int jj = b0 + nt * u;
+        const bool act = jj < nG;
+        if (CLS) {
+          const bool rs = jj >= gL;
+          const uint32_t i = (uint32_t)(rs ? jj - gL : jj), L = (uint32_t)(rs ? gR : gL);
+          const uint64_t pos = rs ? P.segposR : P.segposL, bound = rs ? P.segboundR : P.segboundL;
+          const bool left = rs ? (flags & kGSegRLeft) : (flags & kGSegLLeft);
+          rcv[u] = rs ? (flags & kGSegRRc) : (flags & kGSegLRc);
+          const uint64_t j = rcv[u] ? L - 1u - i : i;
+          bool star;
+          uint64_t g;
+          if (!left) {  // Genome_get_segment_right(left = pos, L, chrhigh = bound)
+            star = pos >= bound || (pos + L >= bound && j + (pos + L - bound) >= L);
+            g = pos + j;
+          } else {      // Genome_get_segment_left(right = pos, L, chroffset = bound)
+            star = pos < bound || (pos < bound + L && j < bound + L - pos);
+            g = pos - L + j;
+          }
+          const uint64_t ptr = (g >> 5) * 3u;
+          cls[u] = star ? kStar : (ptr + 2 >= nwords ? kN : -1);  // beyond the allocation: 'N' (decode_nt)
+          const uint64_t pp = (cls[u] < 0 && act) ? ptr : 0;
+          bit[u] = (uint32_t)(g & 31u);
+          wf[u] = blocks[pp + 2];
+          wv[u] = blocks[pp + (bit[u] < 16 ? 1 : 0)];
+        }
+        if (PRB) {
+#ifdef GMAPDP_GGX_NOME
+          pv[u] = 0.1;  // timing experiment only (make variant): the staging without the MaxEnt evaluation
+#else
+          pv[u] = !act ? 0.0 : sprob ? sprob[P.prob_offset + jj] : gg_site_prob(P, blocks, nwords, metab, jj);
+#endif
+          // a known site has probability 1.0 in the bridge (dynprog_genome.c:2577-2578)
+          if (kn && act && kb[jj]) pv[u] = 1.0;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 2; u++) {
+        const int jj = b0 + nt * u;
+        if (jj >= nG) continue;
+        if (CLS) {
+          int c = cls[u];
+          if (c < 0) {
+            const int x = (int)((wv[u] >> (2u * (bit[u] & 15u))) & 3u);
+            c = ((wf[u] >> bit[u]) & 1u) ? kN : (rcv[u] ? 3 - x : x);  // complement of A C G T is 3 - code
+          }
+          if (jj < gL) gclL[jj + 1] = (uint8_t)c;
+          else gclR[gR - (jj - gL)] = (uint8_t)c;  // rev_gsequenceR[1-c] = segment[glengthR-c]
+        }
+        if (PRB) {
+          if (jj < gL) pL[jj] = pv[u];
+          else pR[jj - gL] = pv[u];
+        }
+      }
+    }
+  };
 #ifdef GMAPDP_GGX_NOSTAGE
   for (int i = tid; i < rlen + 2; i += 128) scL[i] = scR[i] = 0x123456;
   for (int i = tid; i < gL + 2; i += 128) gclL[i] = i & 3;
@@ -771,86 +863,14 @@ __global__ __launch_bounds__(128) GGX_ATTR void gg_kernel(
   for (int i = tid; i < gL; i += 128) pL[i] = 0.1;
   for (int i = tid; i < gR; i += 128) pR[i] = 0.1;
   if (tid < 64) isc[tid] = tid & 7;
-  if (tid == 0) *done = 0;
-  __syncthreads();
-  if (false)
-#endif
-  for (int i = tid; i < rlen; i += 128) {
-    const char c1 = qseq[P.qbase + i];
-    const uint64_t row = *reinterpret_cast<const uint64_t*>(sct + (uint8_t)(c1 & 127) * kNClass);
-    uint32_t w = 0;
-#pragma unroll
-    for (int g = 0; g < 6; g++) w |= (uint32_t)((row >> (8 * g)) & 0xfu) << (4 * g);
-    scL[i + 1] = (int32_t)w;
-    scR[rlen - i] = (int32_t)w;
-  }
-#ifndef GMAPDP_GGX_NOSTAGE
-  if (tid < 2) {
-    scL[tid ? rlen + 1 : 0] = 0;
-    scR[tid ? rlen + 1 : 0] = 0;
-  }
-  // Both segments as one index space jj (L: i = jj, R: i = jj - gL), two items per thread per pass with
-  // every load issued before any is used: segment_nt's bounds (Genome_get_segment_right/left) become a
-  // class or a block address, then the flags word and the half word of each block are loaded together.
-  {
-    const int nG = gL + gR;
-    for (int b0 = tid; b0 < nG; b0 += 256) {
-      uint32_t wf[2], wv[2], bit[2];
-      int cls[2];  // kStar / kN decided from the bounds, -1: decode the words
-      double pv[2];
-      bool rcv[2];
-#pragma unroll
-      for (int u = 0; u < 2; u++) {
-        const int jj = b0 + 128 * u;
-        const bool act = jj < nG;
-        const bool rs = jj >= gL;
-        const uint32_t i = (uint32_t)(rs ? jj - gL : jj), L = (uint32_t)(rs ? gR : gL);
-        const uint64_t pos = rs ? P.segposR : P.segposL, bound = rs ? P.segboundR : P.segboundL;
-        const bool left = rs ? (flags & kGSegRLeft) : (flags & kGSegLLeft);
-        rcv[u] = rs ? (flags & kGSegRRc) : (flags & kGSegLRc);
-        const uint64_t j = rcv[u] ? L - 1u - i : i;
-        bool star;
-        uint64_t g;
-        if (!left) {  // Genome_get_segment_right(left = pos, L, chrhigh = bound)
-          star = pos >= bound || (pos + L >= bound && j + (pos + L - bound) >= L);
-          g = pos + j;
-        } else {      // Genome_get_segment_left(right = pos, L, chroffset = bound)
-          star = pos < bound || (pos < bound + L && j < bound + L - pos);
-          g = pos - L + j;
-        }
-        const uint64_t ptr = (g >> 5) * 3u;
-        cls[u] = star ? kStar : (ptr + 2 >= nwords ? kN : -1);  // beyond the allocation: 'N' (decode_nt)
-        const uint64_t pp = (cls[u] < 0 && act) ? ptr : 0;
-        bit[u] = (uint32_t)(g & 31u);
-        wf[u] = blocks[pp + 2];
-        wv[u] = blocks[pp + (bit[u] < 16 ? 1 : 0)];
-        pv[u] = !act ? 0.0 : sprob ? sprob[P.prob_offset + jj] : gg_site_prob(P, blocks, nwords, metab, jj);
-        // a known site has probability 1.0 in the bridge (dynprog_genome.c:2577-2578)
-        if (kn && act && kb[jj]) pv[u] = 1.0;
-      }
-#pragma unroll
-      for (int u = 0; u < 2; u++) {
-        const int jj = b0 + 128 * u;
-        if (jj >= nG) continue;
-        int c = cls[u];
-        if (c < 0) {
-          const int x = (int)((wv[u] >> (2u * (bit[u] & 15u))) & 3u);
-          c = ((wf[u] >> bit[u]) & 1u) ? kN : (rcv[u] ? 3 - x : x);  // complement of A C G T is 3 - code
-        }
-        if (jj < gL) {
-          gclL[jj + 1] = (uint8_t)c;
-          pL[jj] = pv[u];
-        } else {
-          gclR[gR - (jj - gL)] = (uint8_t)c;  // rev_gsequenceR[1-c] = segment[glengthR-c]
-          pR[jj - gL] = pv[u];
-        }
-      }
-    }
-  }
+#else
+  if (!lazy) stage_scores(tid, 128);
+  if (lazy) stage_segments(true, false, tid, 128);
+  else stage_segments(true, true, tid, 128);
   if (tid < 64) isc[tid] = isctab[(size_t)P.iclass * 128 + ((flags & kGFinal) ? 64 : 0) + tid];
+#endif
   if (tid == 0) *done = 0;
   __syncthreads();
-#endif
   // leftdi[cL] from gsequenceL[cL], [cL+1]; rightdi[cR] from rev_gsequenceR[-cR-1], [-cR] (:2518-2566)
   for (int c = tid; c <= gL; c += 128) ldi[c] = (c < gL - 1) ? left_dinucl(gchL[c + 1], gchL[c + 2]) : 0;
   for (int c = tid; c <= gR; c += 128) rdi[c] = (c < gR - 1) ? right_dinucl(gchR[c + 2], gchR[c + 1]) : 0;
@@ -871,19 +891,30 @@ __global__ __launch_bounds__(128) GGX_ATTR void gg_kernel(
   const int dpi_next = P.dynprogindex + (P.dynprogindex > 0 ? 1 : -1);
 
   // ---- 1. genome_gap_simple (dynprog_genome.c:3006-3280), wave 0 ----
-  if (flags & kGSimple) {
+  if (lazy) {
     if (wave == 0) {
       const bool ok = gg_simple_wave(lane, P, pid, sctab, isctab, cons, qL, qucL, qR, qucR, gclL, gclR, gchL, gchR,
-                                     ldi, rdi, pL, pR, diagL, diagR, out, res, results,
+                                     ldi, rdi, nullptr, nullptr, diagL, diagR, out, res, results,
                                      kn ? kb + gL + gR : nullptr, sprob ? sprob + P.prob_offset : nullptr, blocks,
                                      nwords, metab);
       if (lane == 0) *done = ok ? 1 : 0;
+    } else {
+#ifndef GMAPDP_GGX_NOSTAGE
+      stage_scores(lane, 64);
+#ifndef GMAPDP_GG_PROBS_AFTER_DECLINE
+      stage_segments(false, true, lane, 64);  // (wasted when the test answers; measured faster all the same)
+#endif
+#endif
     }
-    __syncthreads();
+    __syncthreads();  // (both waves, whatever the test answered: `done` is read after it)
     if (*done) {
       GG_MARK_TO(2, 7);
       return;
     }
+#if !defined(GMAPDP_GGX_NOSTAGE) && defined(GMAPDP_GG_PROBS_AFTER_DECLINE)
+    stage_segments(false, true, tid, 128);  // (experiment, make variant: both waves, only once the test declined)
+    __syncthreads();
+#endif
   }
   GG_MARK(2);
 
