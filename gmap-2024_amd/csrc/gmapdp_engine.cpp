@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -261,6 +262,46 @@ struct DevBuf {
   }
 };
 
+// Device memory of a plan or a context: its own allocation (alloc; freed by reset and by the destructor) or
+// a view of memory that someone else frees (another object's, a context's grow-only buffer).  Move-only,
+// and it converts to the pointer it holds.
+template <typename T>
+struct DevMem {
+  DevMem() = default;
+  DevMem(DevMem&& o) noexcept : p(o.p), owned(o.owned) { o.p = nullptr, o.owned = false; }
+  DevMem& operator=(DevMem&& o) noexcept {
+    if (this != &o) {
+      reset();
+      std::swap(p, o.p), std::swap(owned, o.owned);
+    }
+    return *this;
+  }
+  ~DevMem() { reset(); }
+  hipError_t alloc(size_t bytes) {
+    reset();
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), bytes);
+    if (e == hipSuccess) owned = true;
+    else p = nullptr;
+    return e;
+  }
+  void view(T* q) {
+    reset();
+    p = q;
+  }
+  void reset() {
+    if (p && owned) (void)hipFree(p);
+    p = nullptr;
+    owned = false;
+  }
+  bool owns() const { return owned; }
+  T* get() const { return p; }
+  operator T*() const { return p; }
+
+ private:
+  T* p = nullptr;
+  bool owned = false;
+};
+
 // Pinned host staging (hipHostMalloc): the synchronous batch entry points gather every input into
 // one of these and move it with one asynchronous copy each way.
 struct HostBuf {
@@ -300,13 +341,12 @@ struct gmapdp_ctx {
   hipEvent_t ev_fork = nullptr;
   hipEvent_t ev_join[kAux] = {nullptr, nullptr, nullptr};
   Tables* tables = nullptr;
-  int8_t* d_sc = nullptr;
-  uint8_t* d_cs = nullptr;
-  int8_t* d_isc = nullptr;
-  uint32_t* d_genome = nullptr;
+  DevMem<int8_t> d_sc;
+  DevMem<uint8_t> d_cs;
+  DevMem<int8_t> d_isc;
+  DevMem<uint32_t> d_genome;  // its own upload, or a view of a gmapdp_dgenome's / another context's
   uint64_t genome_words = 0;
   uint64_t genome_length = 0;
-  bool genome_owned = true;  // false: another context's HBM genome (gmapdp_share_genome)
   bool one_stream = false;   // GMAPDP_CTX_ONE_STREAM: no side streams (callers that run many contexts)
   int plan_sides = kAux;     // side streams a plan's LPT spreads over (GMAPDP_CTX_TWO_SIDES: 2)
   hipEvent_t ev_block = nullptr;  // GMAPDP_CTX_BLOCKING_SYNC / _POLL_SYNC: batch completion waited on without spinning
@@ -325,6 +365,11 @@ struct gmapdp_ctx {
   DevBuf mxprobs, mxres, mxcands, mxcnt, mxdirect, mxprobs2, mxpairs;  // Dynprog_microexon_int batches
   std::string err;
 };
+
+// the entry points' `void* stream` argument: NULL is the context's own stream
+static hipStream_t stream_of(const gmapdp_ctx* ctx, void* stream) {
+  return stream ? (hipStream_t)stream : ctx->stream;
+}
 
 // Wait for `s`: spinning (hipStreamSynchronize) by default; with GMAPDP_CTX_BLOCKING_SYNC the thread
 // sleeps on a blocking-sync event instead, so that callers running many dispatcher threads next to
@@ -539,9 +584,9 @@ int gmapdp_create_ex(gmapdp_ctx** out, int device, int mode, int user_open, int 
   }
   ctx->tables = new Tables();
   build_tables(*ctx->tables, mode);
-  if (e == hipSuccess) e = hipMalloc(&ctx->d_sc, sizeof(ctx->tables->sc));
-  if (e == hipSuccess) e = hipMalloc(&ctx->d_cs, sizeof(ctx->tables->cs));
-  if (e == hipSuccess) e = hipMalloc(&ctx->d_isc, sizeof(ctx->tables->isc));
+  if (e == hipSuccess) e = ctx->d_sc.alloc(sizeof(ctx->tables->sc));
+  if (e == hipSuccess) e = ctx->d_cs.alloc(sizeof(ctx->tables->cs));
+  if (e == hipSuccess) e = ctx->d_isc.alloc(sizeof(ctx->tables->isc));
   if (e == hipSuccess) e = hipMemcpy(ctx->d_isc, ctx->tables->isc, sizeof(ctx->tables->isc), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(ctx->d_sc, ctx->tables->sc, sizeof(ctx->tables->sc), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(ctx->d_cs, ctx->tables->cs, sizeof(ctx->tables->cs), hipMemcpyHostToDevice);
@@ -557,10 +602,10 @@ void gmapdp_destroy(gmapdp_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)ctx_sync(ctx, ctx->stream);
-  if (ctx->d_sc) (void)hipFree(ctx->d_sc);
-  if (ctx->d_cs) (void)hipFree(ctx->d_cs);
-  if (ctx->d_isc) (void)hipFree(ctx->d_isc);
-  if (ctx->d_genome && ctx->genome_owned) (void)hipFree(ctx->d_genome);
+  ctx->d_sc.reset();
+  ctx->d_cs.reset();
+  ctx->d_isc.reset();
+  ctx->d_genome.reset();
   for (int i = 0; i < gmapdp_ctx::kAux; i++) {
     if (ctx->aux[i]) (void)hipStreamSynchronize(ctx->aux[i]);
     if (ctx->aux[i]) (void)hipStreamDestroy(ctx->aux[i]);
@@ -629,10 +674,7 @@ int gmapdp_set_genome(gmapdp_ctx* ctx, const uint32_t* blocks, size_t nwords, ui
   if (!ctx || !blocks || nwords < (size_t)((length + 31) / 32) * 3) return GMAPDP_EINVAL;
   // coordinates are 64-bit (gmapdp_coord_t): gmapl genomes past 2^32 nt are supported
   (void)hipSetDevice(ctx->device);
-  if (ctx->d_genome && ctx->genome_owned) (void)hipFree(ctx->d_genome);
-  ctx->d_genome = nullptr;
-  ctx->genome_owned = true;
-  hipError_t e = hipMalloc(&ctx->d_genome, nwords * sizeof(uint32_t));
+  hipError_t e = ctx->d_genome.alloc(nwords * sizeof(uint32_t));
   if (e != hipSuccess) return fail(ctx, GMAPDP_ENOMEM, "hipMalloc genome: %s", e);
   e = hipMemcpy(ctx->d_genome, blocks, nwords * sizeof(uint32_t), hipMemcpyHostToDevice);
   if (e != hipSuccess) return fail(ctx, GMAPDP_ENOMEM, "genome upload: %s", e);
@@ -672,7 +714,7 @@ int gmapdp_reserve(gmapdp_ctx* ctx, size_t bytes, int what) {
 
 struct gmapdp_dgenome {
   int device = 0;
-  uint32_t* d = nullptr;
+  DevMem<uint32_t> d;
   uint64_t words = 0, length = 0;
 };
 
@@ -684,12 +726,8 @@ int gmapdp_dgenome_create(int device, const uint32_t* blocks, size_t nwords, uin
   if (hipSetDevice(device) != hipSuccess) return GMAPDP_ENODEV;
   gmapdp_dgenome* g = new gmapdp_dgenome();
   g->device = device;
-  if (hipMalloc(&g->d, nwords * sizeof(uint32_t)) != hipSuccess) {
-    delete g;
-    return GMAPDP_ENOMEM;
-  }
-  if (hipMemcpy(g->d, blocks, nwords * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(g->d);
+  if (g->d.alloc(nwords * sizeof(uint32_t)) != hipSuccess ||
+      hipMemcpy(g->d, blocks, nwords * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
     delete g;
     return GMAPDP_ENOMEM;
   }
@@ -702,18 +740,15 @@ int gmapdp_dgenome_create(int device, const uint32_t* blocks, size_t nwords, uin
 void gmapdp_dgenome_destroy(gmapdp_dgenome* g) {
   if (!g) return;
   (void)hipSetDevice(g->device);
-  if (g->d) (void)hipFree(g->d);
   delete g;
 }
 
 int gmapdp_use_dgenome(gmapdp_ctx* ctx, const gmapdp_dgenome* g) {
   if (!ctx || !g || ctx->device != g->device) return GMAPDP_EINVAL;
   (void)hipSetDevice(ctx->device);
-  if (ctx->d_genome && ctx->genome_owned) (void)hipFree(ctx->d_genome);
-  ctx->d_genome = g->d;
+  ctx->d_genome.view(g->d);
   ctx->genome_words = g->words;
   ctx->genome_length = g->length;
-  ctx->genome_owned = false;
   return GMAPDP_OK;
 }
 
@@ -721,11 +756,9 @@ int gmapdp_share_genome(gmapdp_ctx* ctx, const gmapdp_ctx* owner) {
   if (!ctx || !owner || ctx == owner || ctx->device != owner->device) return GMAPDP_EINVAL;
   if (!owner->d_genome) return GMAPDP_ENOGENOME;
   (void)hipSetDevice(ctx->device);
-  if (ctx->d_genome && ctx->genome_owned) (void)hipFree(ctx->d_genome);
-  ctx->d_genome = owner->d_genome;
+  ctx->d_genome.view(owner->d_genome);
   ctx->genome_words = owner->genome_words;
   ctx->genome_length = owner->genome_length;
-  ctx->genome_owned = false;
   return GMAPDP_OK;
 }
 
@@ -2536,7 +2569,7 @@ struct gmapdp_plan {
   const double* d_sprob = nullptr;            // bound by gmapdp_plan_bind_genome
   gmapdp_genome_result* d_gresults = nullptr;
   const double* d_metab = nullptr;            // gmapdp_plan_bind_genome_maxent: each genome-gap class fills d_sprob
-  void* d_base = nullptr;                     // one allocation holding d_probs, d_order, d_gprobs, d_gorder
+  DevMem<unsigned char> d_base;               // one allocation holding d_probs, d_order, d_gprobs, d_gorder
   // the descriptors' upload, left in flight by gmapdp_plan_create_all (it overlaps the caller's next host
   // work: the stage-2 plan's build); the plan's first run waits for it
   hipEvent_t ev_up = nullptr;
@@ -2548,7 +2581,6 @@ static void plan_free(gmapdp_plan* p) {
     (void)hipEventSynchronize(p->ev_up);
     (void)hipEventDestroy(p->ev_up);
   }
-  if (p->d_base) (void)hipFree(p->d_base);
   delete p;
 }
 
@@ -2609,9 +2641,9 @@ int gmapdp_plan_create_all(gmapdp_ctx* ctx, const gmapdp_single_problem* singles
   size_t o2 = o1 + align_up(sizeof(int) * std::max<size_t>(nd, 1), 256);
   size_t o3 = o2 + align_up(sizeof(DevGenomeProblem) * std::max<size_t>(ng, 1), 256);
   const size_t dtot = o3 + align_up(sizeof(int) * std::max<size_t>(ng, 1), 256);
-  hipError_t e = hipMalloc(&p->d_base, dtot);
+  hipError_t e = p->d_base.alloc(dtot);
   if (e == hipSuccess) {
-    unsigned char* b = (unsigned char*)p->d_base;
+    unsigned char* b = p->d_base;
     p->d_probs = (DevProblem*)b;
     p->d_order = (int*)(b + o1);
     p->d_gprobs = (DevGenomeProblem*)(b + o2);
@@ -2793,8 +2825,7 @@ int gmapdp_plan_run(gmapdp_ctx* ctx, const gmapdp_plan* plan, const char* d_qseq
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   if (!plan->in.gdev.empty() && (!plan->d_sprob || !plan->d_gresults)) return bad(ctx, "genome-gap buffers not bound");
   if (const hipError_t eu = plan_uploaded(plan)) return fail(ctx, GMAPDP_ELAUNCH, "plan upload: %s", eu);
-  return run_plan(ctx, plan->in, plan_args(plan, d_qseq, d_qseq_uc, d_results, d_pairs),
-                  stream ? (hipStream_t)stream : ctx->stream);
+  return run_plan(ctx, plan->in, plan_args(plan, d_qseq, d_qseq_uc, d_results, d_pairs), stream_of(ctx, stream));
 }
 
 static int plan_run_launch(gmapdp_ctx* ctx, const gmapdp_plan* plan, int li, const char* d_qseq,
@@ -2808,7 +2839,7 @@ static int plan_run_launch(gmapdp_ctx* ctx, const gmapdp_plan* plan, int li, con
   }
   if (const hipError_t eu = plan_uploaded(plan)) return fail(ctx, GMAPDP_ELAUNCH, "plan upload: %s", eu);
   hipError_t e = launch_one(ctx, plan->in, li, plan_args(plan, d_qseq, d_qseq_uc, d_results, d_pairs),
-                            stream ? (hipStream_t)stream : ctx->stream, prologue);
+                            stream_of(ctx, stream), prologue);
   if (e != hipSuccess) return fail(ctx, GMAPDP_ELAUNCH, "dp launch: %s", e);
   return GMAPDP_OK;
 }
@@ -2872,7 +2903,7 @@ int gmapdp_compact_pairs(gmapdp_ctx* ctx, const gmapdp_result* d_results, int n,
   if (!ctx || !d_offsets || n < 0 || ng < 0 || (n && !d_results) || (ng && !d_gresults)) return GMAPDP_EINVAL;
   if ((int64_t)n + ng > INT32_MAX) return bad(ctx, "pair compaction: too many lists");
   (void)hipSetDevice(ctx->device);
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   const hipError_t e = launch_pc((const unsigned char*)d_results, n, (int)sizeof(gmapdp_result),
                                  (const unsigned char*)d_gresults, ng, (int)sizeof(gmapdp_genome_result), d_pairs,
                                  (unsigned long long*)d_offsets, (unsigned char*)d_out, s);
@@ -2884,7 +2915,7 @@ int gmapdp_compact_path_pairs(gmapdp_ctx* ctx, const gmapdp_path* d_paths, const
   if (!ctx || !d_offsets || (path_cap && (!d_paths || !d_npaths))) return GMAPDP_EINVAL;
   if (path_cap > (size_t)INT32_MAX) return bad(ctx, "path pair compaction: too many path records");
   (void)hipSetDevice(ctx->device);
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   const hipError_t e = launch_pc_paths(d_paths, (const unsigned long long*)d_npaths, (int)path_cap, d_pairs, pair_cap,
                                        (unsigned long long*)d_offsets, (unsigned char*)d_out, s);
   return e == hipSuccess ? GMAPDP_OK : fail(ctx, GMAPDP_ELAUNCH, "path pair compaction: %s", e);
@@ -2976,6 +3007,80 @@ static int oligo_distinct(const char* q, int qlen, std::vector<uint32_t>& bm) {
   for (uint32_t w : touched) bm[w] = 0;
   return n;
 }
+// get_mappings' event-pool slots a problem's layout counts on, 3 per hit: hits ~ the query's 8-mers once (the
+// locus) plus the window's random matches (4^-8 per position each)
+static size_t oligo_pool_slots(const gmapdp_oligo_problem& p) {
+  const size_t est = (size_t)p.querylength * (2 + (size_t)(oligo_window(p) >> 15)) + 256;
+  return 3 * std::min<size_t>(oligo_table_cap(p), est);
+}
+
+// What the seeding plans and the scan plans decide per problem before they lay anything out.
+struct OligoClasses {
+  std::vector<int> key;       // launch class: 2 * umax + (32-bit counters); umax: the LDS slots for the query's
+                              // distinct 8-mers; 16-bit counters when no count can reach 2^16
+  std::vector<size_t> slots;  // oligo_pool_slots
+  std::map<int, std::vector<int>> classes;  // key -> its problems, in index order
+};
+static const int kBuckets[] = {1024, 2048, 4096, 8192, 16384};  // umax: launch classes by LDS
+
+// Validates the problems and classifies them; the first problem (in index order) the engine rejects decides the
+// message.  major_only: Stage2_scan's rule.
+static int oligo_classify(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problems, int n, const char* qseq_uc,
+                          size_t qbytes, bool major_only, OligoClasses& C) {
+  // each query's distinct 8-mers (plan_threads() host threads: the sweep over a 10 000-read block's 15 850
+  // queries was most of a stage-2 plan's host time)
+  std::vector<int> distinct(n, 0);
+  std::vector<const char*> rej(n, nullptr);
+  plan_parallel((size_t)n, plan_threads((size_t)n * 128), [&](size_t lo, size_t hi, int) {
+    std::vector<uint32_t> bm(2048, 0u);
+    for (size_t i = lo; i < hi; i++) {
+      const gmapdp_oligo_problem& p = problems[i];
+      if (major_only && p.minor)
+        rej[i] = "Stage2_scan takes the major oligoindex only (minor must be 0)";
+      else if (p.querylength <= 8)
+        rej[i] = "stage-2 seeding needs querylength > 8 (Oligoindex_set_inquery)";
+      else if (p.qoff < 0 || (size_t)p.qoff + (size_t)p.querylength > qbytes)
+        rej[i] = "query outside the arena";
+      else
+        distinct[i] = oligo_distinct(qseq_uc + p.qoff, p.querylength, bm);
+    }
+  });
+  C.key.resize(n);
+  C.slots.resize(n);
+  for (int i = 0; i < n; i++) {
+    const gmapdp_oligo_problem& p = problems[i];
+    if (rej[i]) return bad(ctx, rej[i]);
+    const uint64_t win = oligo_window(p);
+    if (win > 0) {  // the last 8-mer start's half-word and the one after it (window8)
+      const uint64_t lpl = (uint64_t)p.chroffset + p.chrend + (p.plusp ? 0 : 1) - 8;
+      const uint64_t h = (lpl >> 4) + 1;
+      if (3 * (h >> 1) + 1 >= ctx->genome_words) return bad(ctx, "stage-2 window past the genome");
+    }
+    if (distinct[i] > kOligoMaxDistinct) return bad(ctx, "query with more than 16384 distinct 8-mers");
+    int umax = kBuckets[0];
+    for (int b : kBuckets)
+      if (distinct[i] <= b) { umax = b; break; }
+    C.key[i] = 2 * umax + (win >= 65536 ? 1 : 0);
+    C.slots[i] = oligo_pool_slots(p);
+    C.classes[C.key[i]].push_back(i);
+  }
+  return GMAPDP_OK;
+}
+
+// The fields of a seeding descriptor that do not depend on the layout (the caller adds its qoff, index,
+// offsets and caps)
+static void oligo_dev_problem(DevOligoProblem& d, const gmapdp_oligo_problem& p, int umax, int mode) {
+  std::memset(&d, 0, sizeof(d));
+  d.querylength = p.querylength;
+  d.chrstart = p.chrstart;
+  d.chrend = p.chrend;
+  d.chroffset = p.chroffset;
+  d.chrhigh = p.chrhigh;
+  d.plusp = p.plusp ? 1 : 0;
+  d.minor = p.minor ? 1 : 0;
+  d.umax = umax;
+  d.reduce = oi_reduction_of(mode, p.plusp != 0);
+}
 
 extern "C" {
 
@@ -3000,13 +3105,13 @@ size_t gmapdp_oligo_diagonal_capacity(const gmapdp_oligo_problem* problems, int 
 // 7 MB of sequential-walk states).
 struct gmapdp_oligo_plan {
   int n = 0;
-  DevOligoProblem* d_probs = nullptr;
-  unsigned char* d_scratch = nullptr;
+  DevMem<DevOligoProblem> d_probs;
+  DevMem<unsigned char> d_scratch;
   std::vector<std::pair<int, int>> launches;  // (first, count) per chunk
   std::vector<int> umax;                      // per chunk: 2 * umax + (32-bit counters)
   std::vector<int> keys;                      // per problem in launch order: its class key
   size_t table_cap = 0, diag_cap = 0, scratch_cap = 0;
-  int32_t* d_nhits = nullptr;                 // sizing runs: each problem's hit-list length
+  DevMem<int32_t> d_nhits;                    // sizing runs: each problem's hit-list length (the context's onhits)
   // Two seeding paths with the same results.  Device-resident plans (a stage-2 plan's sizing run and its
   // runs: bench.py's step, many calls beside the DP classes) take oi_kernel + oi_map_kernel, small-LDS
   // kernels that share the CUs with the DP launches; the synchronous batch APIs (the drop-in's dispatcher
@@ -3015,15 +3120,16 @@ struct gmapdp_oligo_plan {
   bool split = false;
   // get_mappings' event pool (3 slots per hit, shared by a chunk through an atomic cursor; a problem that no
   // longer fits runs the sequential walk in its fallback region, or reports overflow when it has none)
-  uint64_t* d_pool = nullptr;
-  unsigned long long* d_pool_counter = nullptr;
+  DevMem<uint64_t> d_pool;
+  DevMem<unsigned long long> d_pool_counter;
   unsigned long long pool_cap = 0;
-  // A plan made inside a synchronous batch call borrows the context's grow-only buffers: no
+  // A plan made inside a synchronous batch call (`split`) holds views of the context's grow-only buffers: no
   // hipMalloc / hipFree per call (hipFree waits for the whole device, which would serialise the
   // shim's concurrent batches).  `ord` is the host image of d_probs, kept until the plan is freed.
-  // A stage-2 plan's sizing run borrows them as well (tight growth): its upper-bound arenas, tens of GB, are
-  // dropped right after the run, and a fresh hipMalloc of that size per plan took up to a second.
-  bool borrowed = false, sizing = false;
+  // A stage-2 plan's sizing run (`sizing`) views them as well (tight growth): its upper-bound arenas, tens of
+  // GB, are dropped right after the run, and a fresh hipMalloc of that size per plan took up to a second.
+  // Any other plan, and a sizing plan once it is laid out again from its run, allocates its own (oligo_buffers).
+  bool sizing = false;
   std::vector<DevOligoProblem> ord;
   // the Mode_T of the context that made the plan: its descriptors carry that mode's genome reduction, and
   // a plan of a cmet / atoi / ttoc context runs the reducing instantiations of the scan kernels
@@ -3037,20 +3143,6 @@ static constexpr int kOligoChunkProblems = 16384;
 // thousand calls leaves most of the GPU idle); the process pays the first allocation once
 static constexpr size_t kOligoChunkBytes = size_t(3) << 30;
 static constexpr size_t kOligoSizingChunkBytes = size_t(32) << 30;
-
-static void oligo_plan_free(gmapdp_oligo_plan* p) {
-  if (!p) return;
-  if (p->borrowed) {
-    delete p;
-    return;
-  }
-  if (p->d_probs) (void)hipFree(p->d_probs);
-  if (p->d_scratch) (void)hipFree(p->d_scratch);
-  if (p->d_pool) (void)hipFree(p->d_pool);
-  if (p->d_pool_counter) (void)hipFree(p->d_pool_counter);
-  if (p->d_nhits) (void)hipFree(p->d_nhits);
-  delete p;
-}
 
 // Cut the launch-ordered problems into chunks and lay out each chunk's scratch (main region, then the
 // sequential walk's region when `fallback`) and pool, and the table and diagonal arenas: slots[i], tcap[i],
@@ -3108,130 +3200,72 @@ static void oligo_layout(gmapdp_oligo_plan* P, const std::vector<size_t>& slots,
 static hipError_t oligo_buffers(gmapdp_ctx* ctx, gmapdp_oligo_plan* P) {
   const int n = P->n;
   hipError_t e = hipSuccess;
-  if (P->borrowed) {
+  if (P->split || P->sizing) {  // the context's buffers
     const bool t = P->sizing;
     e = ctx->oprobs.ensure(sizeof(DevOligoProblem) * std::max(n, 1));
     if (e == hipSuccess) e = ctx->oscratch.ensure(std::max<size_t>(P->scratch_cap, 256), t);
     if (e == hipSuccess) e = ctx->opool.ensure(sizeof(uint64_t) * std::max<size_t>(P->pool_cap, 1), t);
     if (e == hipSuccess) e = ctx->opoolctr.ensure(sizeof(unsigned long long));
-    P->d_probs = (DevOligoProblem*)ctx->oprobs.p;
-    P->d_scratch = (unsigned char*)ctx->oscratch.p;
-    P->d_pool = (uint64_t*)ctx->opool.p;
-    P->d_pool_counter = (unsigned long long*)ctx->opoolctr.p;
+    P->d_probs.view((DevOligoProblem*)ctx->oprobs.p);
+    P->d_scratch.view((unsigned char*)ctx->oscratch.p);
+    P->d_pool.view((uint64_t*)ctx->opool.p);
+    P->d_pool_counter.view((unsigned long long*)ctx->opoolctr.p);
     if (e == hipSuccess && n)
       e = hipMemcpyAsync(P->d_probs, P->ord.data(), sizeof(DevOligoProblem) * n, hipMemcpyHostToDevice, ctx->stream);
     return e;
   }
-  for (void** b : {(void**)&P->d_scratch, (void**)&P->d_pool}) {
-    if (*b) (void)hipFree(*b);
-    *b = nullptr;
-  }
-  if (!P->d_probs) e = hipMalloc(&P->d_probs, sizeof(DevOligoProblem) * std::max(n, 1));
-  if (e == hipSuccess) e = hipMalloc(&P->d_scratch, std::max<size_t>(P->scratch_cap, 256));
-  if (e == hipSuccess) e = hipMalloc(&P->d_pool, sizeof(uint64_t) * std::max<size_t>(P->pool_cap, 1));
-  if (e == hipSuccess && !P->d_pool_counter) e = hipMalloc(&P->d_pool_counter, sizeof(unsigned long long));
+  // the plan's own: a new layout takes a new scratch and pool, and keeps descriptors and cursor it already owns
+  P->d_scratch.reset();
+  P->d_pool.reset();
+  if (!P->d_probs.owns()) e = P->d_probs.alloc(sizeof(DevOligoProblem) * std::max(n, 1));
+  if (e == hipSuccess) e = P->d_scratch.alloc(std::max<size_t>(P->scratch_cap, 256));
+  if (e == hipSuccess) e = P->d_pool.alloc(sizeof(uint64_t) * std::max<size_t>(P->pool_cap, 1));
+  if (e == hipSuccess && !P->d_pool_counter.owns()) e = P->d_pool_counter.alloc(sizeof(unsigned long long));
   if (e == hipSuccess && n)
     e = hipMemcpy(P->d_probs, P->ord.data(), sizeof(DevOligoProblem) * n, hipMemcpyHostToDevice);
   return e;
 }
 
 static int oligo_plan_build(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problems, int n, const char* qseq_uc,
-                            size_t qbytes, gmapdp_oligo_plan** plan, bool borrow, bool sizing = false) {
-  if (!ctx || !plan || n < 0 || (n > 0 && (!problems || !qseq_uc))) return GMAPDP_EINVAL;
-  *plan = nullptr;
+                            size_t qbytes, std::unique_ptr<gmapdp_oligo_plan>& plan, bool split,
+                            bool sizing = false) {
+  plan.reset();
   // stage 2 exists in STANDARD and the three stranded modes; GMAP itself refuses the non-stranded ones
   if (oi_reduction_of(ctx->mode, true) < 0)
     return bad(ctx, "stage 2 in a non-stranded cmet / atoi / ttoc mode (GMAP supports the stranded modes only)");
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   (void)hipSetDevice(ctx->device);
-  std::vector<DevOligoProblem> dev(n);
-  std::vector<size_t> slots(n), tcap(n), dcap(n);
-  size_t toff = 0;
-  static const int kBuckets[] = {1024, 2048, 4096, 8192, 16384};  // launch classes by LDS
-  std::map<int, std::vector<int>> classes;
-  const char* ev = std::getenv("GMAPDP_OLIGO_POOL_SLOTS");  // tests: a small pool forces the sequential walk
-  // each query's distinct 8-mers (plan_threads() host threads: the sweep over a 10 000-read block's 15 850
-  // queries was most of a stage-2 plan's host time), and the first problem the engine rejects
-  std::vector<int> distinct(n, 0);
-  std::vector<const char*> rej(n, nullptr);
-  const int T = plan_threads((size_t)n * 128);
-  plan_parallel((size_t)n, T, [&](size_t lo, size_t hi, int) {
-    std::vector<uint32_t> bm(2048, 0u);
-    for (size_t i = lo; i < hi; i++) {
-      const gmapdp_oligo_problem& p = problems[i];
-      if (p.querylength <= 8) {
-        rej[i] = "stage-2 seeding needs querylength > 8 (Oligoindex_set_inquery)";
-        continue;
-      }
-      if (p.qoff < 0 || (size_t)p.qoff + (size_t)p.querylength > qbytes) {
-        rej[i] = "query outside the arena";
-        continue;
-      }
-      distinct[i] = oligo_distinct(qseq_uc + p.qoff, p.querylength, bm);
-    }
-  });
+  OligoClasses C;
+  if (int rc = oligo_classify(ctx, problems, n, qseq_uc, qbytes, false, C)) return rc;
+  std::vector<size_t> tcap(n), dcap(n);
   for (int i = 0; i < n; i++) {
-    const gmapdp_oligo_problem& p = problems[i];
-    if (rej[i]) return bad(ctx, rej[i]);
-    const uint64_t win = oligo_window(p);
-    if (win > 0) {  // the last 8-mer start's half-word and the one after it (window8)
-      const uint64_t lpl = (uint64_t)p.chroffset + p.chrend + (p.plusp ? 0 : 1) - 8;
-      const uint64_t h = (lpl >> 4) + 1;
-      if (3 * (h >> 1) + 1 >= ctx->genome_words) return bad(ctx, "stage-2 window past the genome");
-    }
-    const int U = distinct[i];
-    if (U > kOligoMaxDistinct) return bad(ctx, "query with more than 16384 distinct 8-mers");
-    int umax = kBuckets[0];
-    for (int b : kBuckets)
-      if (U <= b) { umax = b; break; }
-    DevOligoProblem& d = dev[i];
-    std::memset(&d, 0, sizeof(d));
-    d.qoff = p.qoff;
-    d.querylength = p.querylength;
-    d.chrstart = p.chrstart;
-    d.chrend = p.chrend;
-    d.chroffset = p.chroffset;
-    d.chrhigh = p.chrhigh;
-    d.plusp = p.plusp ? 1 : 0;
-    d.minor = p.minor ? 1 : 0;
-    d.umax = umax;
-    d.index = i;
-    d.reduce = oi_reduction_of(ctx->mode, p.plusp != 0);
-    tcap[i] = oligo_table_cap(p);
-    dcap[i] = oligo_diag_cap(p);
-    toff += tcap[i];
-    // hits ~ the query's 8-mers once (the locus) plus the window's random matches (4^-8 per position each)
-    const size_t est = (size_t)p.querylength * (2 + (size_t)(win >> 15)) + 256;
-    slots[i] = 3 * std::min<size_t>(oligo_table_cap(p), est);
-    // launch class: (umax, 32-bit counters); 16-bit counters when no count can reach 2^16
-    classes[2 * umax + (win >= 65536 ? 1 : 0)].push_back(i);
+    tcap[i] = oligo_table_cap(problems[i]);
+    dcap[i] = oligo_diag_cap(problems[i]);
   }
-  gmapdp_oligo_plan* P = new gmapdp_oligo_plan();
+  std::unique_ptr<gmapdp_oligo_plan> P(new gmapdp_oligo_plan());
   P->n = n;
   P->mode = ctx->mode;
-  P->split = borrow;
-  P->borrowed = borrow || sizing;
+  P->split = split;
   P->sizing = sizing;
-  P->ord.reserve(n);
-  for (auto& kv : classes)
+  P->ord.resize(n);
+  P->keys.reserve(n);
+  for (auto& kv : C.classes)
     for (int i : kv.second) {
-      P->ord.push_back(dev[i]);
+      DevOligoProblem& d = P->ord[P->keys.size()];
+      oligo_dev_problem(d, problems[i], kv.first >> 1, ctx->mode);
+      d.qoff = problems[i].qoff;
+      d.index = i;
       P->keys.push_back(kv.first);
     }
   // (a sizing run keeps no sequential-walk region -- ~70 % of its scratch, the difference between one launch
   // and four for a 10 000-read block; a call that exhausts its chunk's event pool there reports overflow, and
   // the re-layout gives it the diagonal arena's upper bound instead of a measured count)
-  oligo_layout(P, slots, !sizing, tcap, dcap, sizing);
-  // (the kernels' mappings are relative to each problem's table_offset: the arena may pass 2^31 entries;
-  // the public seeding API, whose mappings are absolute 32-bit indexes, checks its own total)
-  (void)toff;
-  if (ev) P->pool_cap = std::strtoull(ev, nullptr, 10);  // per chunk
-  const hipError_t e = oligo_buffers(ctx, P);
-  if (e != hipSuccess) {
-    oligo_plan_free(P);
-    return fail(ctx, GMAPDP_ENOMEM, "oligo plan: %s", e);
-  }
-  *plan = P;
+  oligo_layout(P.get(), C.slots, !sizing, tcap, dcap, sizing);
+  // tests: a small pool (per chunk) forces the sequential walk
+  if (const char* ev = std::getenv("GMAPDP_OLIGO_POOL_SLOTS")) P->pool_cap = std::strtoull(ev, nullptr, 10);
+  const hipError_t e = oligo_buffers(ctx, P.get());
+  if (e != hipSuccess) return fail(ctx, GMAPDP_ENOMEM, "oligo plan: %s", e);
+  plan = std::move(P);
   return GMAPDP_OK;
 }
 
@@ -3273,14 +3307,10 @@ static hipError_t oligo_plan_relayout(gmapdp_ctx* ctx, gmapdp_oligo_plan* P, con
   }
   // the hit lists sized as measured (a few % of a 214-kb window), so one launch holds most of a plan
   oligo_layout(P, slots, false, tcap, dcap, false, &hcap);
-  if (P->borrowed) {  // the sizing run's borrowed buffers stay the context's; the plan allocates its own
-    P->borrowed = P->sizing = false;
-    P->d_probs = nullptr;
-    P->d_scratch = nullptr;
-    P->d_pool = nullptr;
-    P->d_pool_counter = nullptr;
-    P->d_nhits = nullptr;
-  }
+  // the sizing run's views stay the context's memory; the plan's runs take buffers of their own and measure
+  // no hit lists
+  P->sizing = false;
+  P->d_nhits.reset();
   return oligo_buffers(ctx, P);
 }
 
@@ -3288,7 +3318,11 @@ extern "C" {
 
 int gmapdp_oligo_plan_create(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problems, int n, const char* qseq_uc,
                              size_t qbytes, gmapdp_oligo_plan** plan) {
-  return oligo_plan_build(ctx, problems, n, qseq_uc, qbytes, plan, false);
+  if (!ctx || !plan || n < 0 || (n > 0 && (!problems || !qseq_uc))) return GMAPDP_EINVAL;
+  std::unique_ptr<gmapdp_oligo_plan> p;
+  const int rc = oligo_plan_build(ctx, problems, n, qseq_uc, qbytes, p, false);
+  *plan = p.release();
+  return rc;
 }
 
 // The device mappings are relative to each problem's table_offset; the host-array API hands out absolute
@@ -3306,7 +3340,7 @@ static void oligo_absolute_mappings(const gmapdp_oligo_problem* problems, int n,
 size_t gmapdp_oligo_plan_positions_capacity(const gmapdp_oligo_plan* plan) { return plan ? plan->table_cap : 0; }
 size_t gmapdp_oligo_plan_diagonal_capacity(const gmapdp_oligo_plan* plan) { return plan ? plan->diag_cap : 0; }
 int gmapdp_oligo_plan_nlaunches(const gmapdp_oligo_plan* plan) { return plan ? (int)plan->launches.size() : 0; }
-void gmapdp_oligo_plan_destroy(gmapdp_oligo_plan* plan) { oligo_plan_free(plan); }
+void gmapdp_oligo_plan_destroy(gmapdp_oligo_plan* plan) { delete plan; }
 
 int gmapdp_oligo_plan_run(gmapdp_ctx* ctx, const gmapdp_oligo_plan* plan, const char* d_qseq_uc,
                           gmapdp_oligo_result* d_results, int32_t* d_npositions, int32_t* d_mappings,
@@ -3315,7 +3349,7 @@ int gmapdp_oligo_plan_run(gmapdp_ctx* ctx, const gmapdp_oligo_plan* plan, const 
   if (plan->mode != ctx->mode) return bad(ctx, "an oligo plan made by a context of another mode");
   if (plan->n == 0) return GMAPDP_OK;
   (void)hipSetDevice(ctx->device);
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   const bool modal = plan->mode != 0;
   for (size_t li = 0; li < plan->launches.size(); li++) {
     // the chunks reuse one scratch and one pool, in stream order
@@ -3354,18 +3388,16 @@ int gmapdp_oligo_mappings_batch(gmapdp_ctx* ctx, const gmapdp_oligo_problem* pro
     for (int i = 1; i < n; i++)
       if (sl[i].first < sl[i - 1].second) return bad(ctx, "stage-2 seeding: two problems share query slots");
   }
-  gmapdp_oligo_plan* plan = nullptr;
-  int rc = oligo_plan_build(ctx, problems, n, qseq_uc, qbytes, &plan, true);
+  std::unique_ptr<gmapdp_oligo_plan> plan;  // (views of the context's buffers: nothing to free)
+  int rc = oligo_plan_build(ctx, problems, n, qseq_uc, qbytes, plan, true);
   if (rc) return rc;
   const size_t toff = plan->table_cap, doff = plan->diag_cap;
-  if (toff > 0x7fffffffull) {  // absolute 32-bit mappings
-    oligo_plan_free(plan);
+  // (the kernels' mappings are relative to each problem's table_offset, so a plan's arena may pass 2^31
+  // entries; this API's mappings are absolute 32-bit indexes)
+  if (toff > 0x7fffffffull)
     return bad(ctx, "stage-2 seeding: table arena beyond 2^31 entries (split the batch)");
-  }
-  if (toff > positions_capacity || doff > diagonal_capacity || (toff && !positions) || (doff && !diagonals)) {
-    oligo_plan_free(plan);
+  if (toff > positions_capacity || doff > diagonal_capacity || (toff && !positions) || (doff && !diagonals))
     return bad(ctx, "positions or diagonal arena too small");
-  }
   hipError_t e = ctx->oresults.ensure(sizeof(gmapdp_oligo_result) * n);
   if (e == hipSuccess) e = ctx->onpos.ensure(sizeof(int32_t) * qbytes);
   if (e == hipSuccess) e = ctx->omap.ensure(sizeof(int32_t) * qbytes);
@@ -3378,16 +3410,12 @@ int gmapdp_oligo_mappings_batch(gmapdp_ctx* ctx, const gmapdp_oligo_problem* pro
   // this API copies back to the caller whole)
   if (e == hipSuccess) e = hipMemsetAsync(ctx->onpos.p, 0, sizeof(int32_t) * qbytes, s);
   if (e == hipSuccess) e = hipMemsetAsync(ctx->omap.p, 0xff, sizeof(int32_t) * qbytes, s);
-  if (e != hipSuccess) {
-    oligo_plan_free(plan);
-    return fail(ctx, GMAPDP_ENOMEM, "oligo buffers: %s", e);
-  }
-  rc = gmapdp_oligo_plan_run(ctx, plan, (const char*)ctx->qseq_uc.p, (gmapdp_oligo_result*)ctx->oresults.p,
+  if (e != hipSuccess) return fail(ctx, GMAPDP_ENOMEM, "oligo buffers: %s", e);
+  rc = gmapdp_oligo_plan_run(ctx, plan.get(), (const char*)ctx->qseq_uc.p, (gmapdp_oligo_result*)ctx->oresults.p,
                              (int32_t*)ctx->onpos.p, (int32_t*)ctx->omap.p, (uint32_t*)ctx->otable.p,
                              (int32_t*)ctx->odiag.p, nullptr);
   if (rc) {
     (void)ctx_sync(ctx, s);
-    oligo_plan_free(plan);
     return rc;
   }
   e = hipMemcpyAsync(results, ctx->oresults.p, sizeof(gmapdp_oligo_result) * n, hipMemcpyDeviceToHost, s);
@@ -3398,7 +3426,6 @@ int gmapdp_oligo_mappings_batch(gmapdp_ctx* ctx, const gmapdp_oligo_problem* pro
   if (e == hipSuccess && doff)
     e = hipMemcpyAsync(diagonals, ctx->odiag.p, 4 * sizeof(int32_t) * doff, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = ctx_sync(ctx, s);
-  oligo_plan_free(plan);
   if (e != hipSuccess) return fail(ctx, GMAPDP_ELAUNCH, "oligo execution: %s", e);
   oligo_absolute_mappings(problems, n, results, mappings);
   return GMAPDP_OK;
@@ -3420,9 +3447,9 @@ struct ScanLaunch {
 };
 struct gmapdp_scan_plan {
   int n = 0, mode = 0;
-  DevOligoProblem* d_probs = nullptr;
-  unsigned char* d_extra = nullptr;           // DevScanExtra per problem, launch order
-  unsigned char* d_arena = nullptr;           // arena_bytes + the pool cursor + the overflow flag
+  DevMem<DevOligoProblem> d_probs;
+  DevMem<unsigned char> d_extra;              // DevScanExtra per problem, launch order
+  DevMem<unsigned char> d_arena;              // arena_bytes + the pool cursor + the overflow flag
   size_t arena_bytes = 0, budget = 0;
   std::vector<ScanLaunch> launches;
 };
@@ -3441,14 +3468,6 @@ static size_t scan_budget(gmapdp_ctx* ctx) {
   return std::max(held, kScanBudgetFloor);
 }
 
-static void scan_plan_free(gmapdp_scan_plan* p) {
-  if (!p) return;
-  if (p->d_probs) (void)hipFree(p->d_probs);
-  if (p->d_extra) (void)hipFree(p->d_extra);
-  if (p->d_arena) (void)hipFree(p->d_arena);
-  delete p;
-}
-
 extern "C" {
 
 int gmapdp_scan_plan_create(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problems, int n, const char* qseq_uc,
@@ -3459,41 +3478,9 @@ int gmapdp_scan_plan_create(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problem
     return bad(ctx, "stage 2 in a non-stranded cmet / atoi / ttoc mode (GMAP supports the stranded modes only)");
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   (void)hipSetDevice(ctx->device);
-  // validation, distinct 8-mers and launch classes as the seeding plans make them (oligo_plan_build)
-  std::vector<int> distinct(n, 0);
-  std::vector<const char*> rej(n, nullptr);
-  plan_parallel((size_t)n, plan_threads((size_t)n * 128), [&](size_t lo, size_t hi, int) {
-    std::vector<uint32_t> bm(2048, 0u);
-    for (size_t i = lo; i < hi; i++) {
-      const gmapdp_oligo_problem& p = problems[i];
-      if (p.minor)
-        rej[i] = "Stage2_scan takes the major oligoindex only (minor must be 0)";
-      else if (p.querylength <= 8)
-        rej[i] = "stage-2 seeding needs querylength > 8 (Oligoindex_set_inquery)";
-      else if (p.qoff < 0 || (size_t)p.qoff + (size_t)p.querylength > qbytes)
-        rej[i] = "query outside the arena";
-      else
-        distinct[i] = oligo_distinct(qseq_uc + p.qoff, p.querylength, bm);
-    }
-  });
-  static const int kBuckets[] = {1024, 2048, 4096, 8192, 16384};
-  std::map<int, std::vector<int>> classes;
-  for (int i = 0; i < n; i++) {
-    const gmapdp_oligo_problem& p = problems[i];
-    if (rej[i]) return bad(ctx, rej[i]);
-    const uint64_t win = oligo_window(p);
-    if (win > 0) {
-      const uint64_t lpl = (uint64_t)p.chroffset + p.chrend + (p.plusp ? 0 : 1) - 8;
-      const uint64_t h = (lpl >> 4) + 1;
-      if (3 * (h >> 1) + 1 >= ctx->genome_words) return bad(ctx, "stage-2 window past the genome");
-    }
-    if (distinct[i] > kOligoMaxDistinct) return bad(ctx, "query with more than 16384 distinct 8-mers");
-    int umax = kBuckets[0];
-    for (int b : kBuckets)
-      if (distinct[i] <= b) { umax = b; break; }
-    classes[2 * umax + (win >= 65536 ? 1 : 0)].push_back(i);
-  }
-  gmapdp_scan_plan* P = new gmapdp_scan_plan();
+  OligoClasses C;
+  if (int rc = oligo_classify(ctx, problems, n, qseq_uc, qbytes, /*major_only*/ true, C)) return rc;
+  std::unique_ptr<gmapdp_scan_plan> P(new gmapdp_scan_plan());
   P->n = n;
   P->mode = ctx->mode;
   P->budget = scan_budget(ctx);
@@ -3525,18 +3512,16 @@ int gmapdp_scan_plan_create(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problem
     L.first = (int)ord.size();
     cs = cp = ct = cd = cq = 0;
   };
-  for (auto& kv : classes)
+  for (auto& kv : C.classes)
     for (int i : kv.second) {
       const gmapdp_oligo_problem& p = problems[i];
       const uint32_t w = p.chrend > p.chrstart ? p.chrend - p.chrstart : 0;
       const size_t mb = align_up(scratch_bytes_oi(p.querylength, w), 256);
       const size_t fb = align_up(scratch_bytes_oi_fallback(p.querylength, w), 256);
       const size_t tcap = oligo_table_cap(p), dcap = oligo_diag_cap(p);
-      const uint64_t win = oligo_window(p);
       // (the event pool's share as the seeding plans estimate it; a problem with more events than the
       // sub-batch's pool has left walks the query sequentially in its fallback region: never an overflow)
-      const size_t est = (size_t)p.querylength * (2 + (size_t)(win >> 15)) + 256;
-      const size_t slots = 3 * std::min<size_t>(tcap, est);
+      const size_t slots = C.slots[i];
       const size_t qpad = align_up((size_t)p.querylength, 16);
       const size_t bytes = mb + fb + 8 * slots + 4 * tcap + 16 * dcap + 9 * qpad + sizeof(gmapdp_oligo_result) + 8 * 256;
       const size_t open = cs + 8 * cp + 4 * ct + 16 * cd + 9 * cq + sizeof(gmapdp_oligo_result) * (size_t)L.count + 8 * 256;
@@ -3546,16 +3531,8 @@ int gmapdp_scan_plan_create(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problem
         close();
       if (L.count == 0) L.key = kv.first;
       DevOligoProblem d;
-      std::memset(&d, 0, sizeof(d));
+      oligo_dev_problem(d, p, kv.first >> 1, ctx->mode);
       d.qoff = (int32_t)cq;  // the sub-batch's private query arena
-      d.querylength = p.querylength;
-      d.chrstart = p.chrstart;
-      d.chrend = p.chrend;
-      d.chroffset = p.chroffset;
-      d.chrhigh = p.chrhigh;
-      d.plusp = p.plusp ? 1 : 0;
-      d.minor = 0;
-      d.umax = kv.first >> 1;
       d.index = L.count;     // its seeding record within the sub-batch
       d.table_offset = (int64_t)ct;
       d.diag_offset = (int64_t)cd;
@@ -3564,7 +3541,6 @@ int gmapdp_scan_plan_create(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problem
       d.hit_cap = (uint32_t)std::min<size_t>((size_t)w + 2, 0xffffffffu);
       d.table_cap = (uint32_t)std::min<size_t>(tcap, 0xffffffffu);
       d.diag_cap = (uint32_t)std::min<size_t>(dcap, 0xffffffffu);
-      d.reduce = oi_reduction_of(ctx->mode, p.plusp != 0);
       ord.push_back(d);
       extra.push_back(Extra{p.qoff, i});
       cs += mb + fb;
@@ -3577,24 +3553,21 @@ int gmapdp_scan_plan_create(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problem
   close();
   hipError_t e = hipSuccess;
   if (n) {
-    e = hipMalloc(&P->d_probs, sizeof(DevOligoProblem) * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc(&P->d_extra, sizeof(Extra) * (size_t)n);
+    e = P->d_probs.alloc(sizeof(DevOligoProblem) * (size_t)n);
+    if (e == hipSuccess) e = P->d_extra.alloc(sizeof(Extra) * (size_t)n);
     // (the pool cursor and the overflow flag follow the arena)
-    if (e == hipSuccess) e = hipMalloc(&P->d_arena, P->arena_bytes + 256);
+    if (e == hipSuccess) e = P->d_arena.alloc(P->arena_bytes + 256);
     if (e == hipSuccess) e = hipMemcpy(P->d_probs, ord.data(), sizeof(DevOligoProblem) * (size_t)n, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(P->d_extra, extra.data(), sizeof(Extra) * (size_t)n, hipMemcpyHostToDevice);
   }
-  if (e != hipSuccess) {
-    scan_plan_free(P);
-    return fail(ctx, GMAPDP_ENOMEM, "scan plan: %s", e);
-  }
-  *plan = P;
+  if (e != hipSuccess) return fail(ctx, GMAPDP_ENOMEM, "scan plan: %s", e);
+  *plan = P.release();
   return GMAPDP_OK;
 }
 
 int gmapdp_scan_plan_nlaunches(const gmapdp_scan_plan* plan) { return plan ? (int)plan->launches.size() : 0; }
 size_t gmapdp_scan_plan_scratch_bytes(const gmapdp_scan_plan* plan) { return plan ? plan->arena_bytes : 0; }
-void gmapdp_scan_plan_destroy(gmapdp_scan_plan* plan) { scan_plan_free(plan); }
+void gmapdp_scan_plan_destroy(gmapdp_scan_plan* plan) { delete plan; }
 
 int gmapdp_scan_plan_run(gmapdp_ctx* ctx, const gmapdp_scan_plan* plan, const char* d_qseq_uc,
                          gmapdp_scan_result* d_results, void* stream) {
@@ -3603,7 +3576,7 @@ int gmapdp_scan_plan_run(gmapdp_ctx* ctx, const gmapdp_scan_plan* plan, const ch
   if (plan->n == 0) return GMAPDP_OK;
   if (!d_qseq_uc || !d_results) return GMAPDP_EINVAL;
   (void)hipSetDevice(ctx->device);
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   unsigned char* A = plan->d_arena;
   unsigned long long* pool_counter = reinterpret_cast<unsigned long long*>(A + plan->arena_bytes);
   int32_t* flag = reinterpret_cast<int32_t*>(A + plan->arena_bytes + 64);
@@ -3629,18 +3602,13 @@ int gmapdp_stage2_scan_batch(gmapdp_ctx* ctx, const gmapdp_oligo_problem* proble
   gmapdp_scan_plan* plan = nullptr;
   int rc = gmapdp_scan_plan_create(ctx, problems, n, qseq_uc, qbytes, &plan);
   if (rc) return rc;
-  if (n == 0) {
-    scan_plan_free(plan);
-    return GMAPDP_OK;
-  }
+  std::unique_ptr<gmapdp_scan_plan> plan_holder(plan);
+  if (n == 0) return GMAPDP_OK;
   hipStream_t s = ctx->stream;
   hipError_t e = ctx->qseq_uc.ensure(qbytes);
   if (e == hipSuccess) e = ctx->oresults.ensure(sizeof(gmapdp_scan_result) * (size_t)n);
   if (e == hipSuccess) e = hipMemcpyAsync(ctx->qseq_uc.p, qseq_uc, qbytes, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) {
-    scan_plan_free(plan);
-    return fail(ctx, GMAPDP_ENOMEM, "scan buffers: %s", e);
-  }
+  if (e != hipSuccess) return fail(ctx, GMAPDP_ENOMEM, "scan buffers: %s", e);
   rc = gmapdp_scan_plan_run(ctx, plan, (const char*)ctx->qseq_uc.p, (gmapdp_scan_result*)ctx->oresults.p, nullptr);
   int32_t overflow = 0;
   if (rc == GMAPDP_OK) {
@@ -3648,8 +3616,8 @@ int gmapdp_stage2_scan_batch(gmapdp_ctx* ctx, const gmapdp_oligo_problem* proble
     if (e == hipSuccess)
       e = hipMemcpyAsync(&overflow, plan->d_arena + plan->arena_bytes + 64, sizeof(int32_t), hipMemcpyDeviceToHost, s);
   }
-  const hipError_t es = ctx_sync(ctx, s);  // (also before the plan's buffers are freed)
-  scan_plan_free(plan);
+  const hipError_t es = ctx_sync(ctx, s);
+  plan_holder.reset();  // (after the wait: its hipFrees)
   if (rc) return rc;
   if (e == hipSuccess) e = es;
   if (e != hipSuccess) return fail(ctx, GMAPDP_ELAUNCH, "scan execution: %s", e);
@@ -3680,6 +3648,44 @@ static int s2_batch_flags(gmapdp_ctx* ctx, const gmapdp_stage2_problem* problems
   return GMAPDP_OK;
 }
 
+// What both Stage2_compute entry points do before they plan the seeding: the flags (s2_batch_flags), then every
+// problem's maxintronlen; op: the seeding problems, dp: the chaining descriptors (their scratch not laid out
+// yet), *qsum: the query lengths' sum.
+static int s2_problems(gmapdp_ctx* ctx, const gmapdp_stage2_problem* problems, int n, const double** metab,
+                       std::vector<gmapdp_oligo_problem>& op, std::vector<DevStage2Problem>& dp, size_t* qsum) {
+  if (int rc = s2_batch_flags(ctx, problems, n, metab)) return rc;
+  op.resize(n);
+  dp.resize(n);
+  *qsum = 0;
+  for (int i = 0; i < n; i++) {
+    const gmapdp_stage2_problem& p = problems[i];
+    if (p.maxintronlen < 0) return bad(ctx, "stage 2: negative maxintronlen");
+    // (minor 0: Stage2_compute takes oligoindices_major, gmap.c:1211)
+    op[i] = gmapdp_oligo_problem{p.qoff, p.querylength, p.chrstart, p.chrend, p.chroffset, p.chrhigh,
+                                 p.plusp ? 1 : 0, 0};
+    dp[i] = DevStage2Problem{p.qoff, p.querylength, p.chrstart, p.chrend, p.chroffset, p.chrhigh, p.plusp ? 1 : 0,
+                             p.splicingp ? 1 : 0, (uint32_t)p.maxintronlen, i, 0};
+    *qsum += (size_t)p.querylength;
+  }
+  return GMAPDP_OK;
+}
+
+// The end of a Stage2_compute fetch: np path records and nq pair records of the device pools into the caller's
+// arrays (GMAPDP_ESPACE when they do not fit, *paths_needed / *pairs_needed saying what would), then the wait.
+static int s2_copy_out(gmapdp_ctx* ctx, hipStream_t s, const gmapdp_path* d_paths, size_t np,
+                       const gmapdp_path_pair* d_pairs, size_t nq, gmapdp_path* paths, size_t path_cap,
+                       gmapdp_path_pair* pairs, size_t pair_cap, size_t* paths_needed, size_t* pairs_needed,
+                       const char* errfmt) {
+  if (paths_needed) *paths_needed = np;
+  if (pairs_needed) *pairs_needed = nq;
+  if (np > path_cap || nq > pair_cap || (np && !paths) || (nq && !pairs)) return GMAPDP_ESPACE;
+  hipError_t e = hipSuccess;
+  if (np) e = hipMemcpyAsync(paths, d_paths, sizeof(gmapdp_path) * np, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && nq) e = hipMemcpyAsync(pairs, d_pairs, sizeof(gmapdp_path_pair) * nq, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = ctx_sync(ctx, s);
+  return e == hipSuccess ? GMAPDP_OK : fail(ctx, GMAPDP_ELAUNCH, errfmt, e);
+}
+
 extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem* problems, int n, const char* qseq,
                                    const char* qseq_uc, size_t qbytes, gmapdp_stage2_result* results,
                                    gmapdp_path* paths, size_t path_cap, gmapdp_path_pair* pairs, size_t pair_cap,
@@ -3691,35 +3697,13 @@ extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem*
   if (n == 0) return GMAPDP_OK;
   (void)hipSetDevice(ctx->device);
   const double* canon_metab = nullptr;
-  if (int frc = s2_batch_flags(ctx, problems, n, &canon_metab)) return frc;
-  std::vector<gmapdp_oligo_problem> op(n);
-  std::vector<DevStage2Problem> dp(n);
-  for (int i = 0; i < n; i++) {
-    const gmapdp_stage2_problem& p = problems[i];
-    if (p.maxintronlen < 0) return bad(ctx, "stage 2: negative maxintronlen");
-    op[i].qoff = p.qoff;
-    op[i].querylength = p.querylength;
-    op[i].chrstart = p.chrstart;
-    op[i].chrend = p.chrend;
-    op[i].chroffset = p.chroffset;
-    op[i].chrhigh = p.chrhigh;
-    op[i].plusp = p.plusp ? 1 : 0;
-    op[i].minor = 0;  // Stage2_compute takes oligoindices_major (gmap.c:1211)
-    DevStage2Problem& d = dp[i];
-    d.qoff = p.qoff;
-    d.querylength = p.querylength;
-    d.chrstart = p.chrstart;
-    d.chrend = p.chrend;
-    d.chroffset = p.chroffset;
-    d.chrhigh = p.chrhigh;
-    d.plusp = p.plusp ? 1 : 0;
-    d.splicingp = p.splicingp ? 1 : 0;
-    d.maxintronlen = (uint32_t)p.maxintronlen;
-    d.index = i;
-    d.scratch_offset = 0;
-  }
-  gmapdp_oligo_plan* plan = nullptr;
-  int rc = oligo_plan_build(ctx, op.data(), n, qseq_uc, qbytes, &plan, true);
+  std::vector<gmapdp_oligo_problem> op;
+  std::vector<DevStage2Problem> dp;
+  size_t qsum = 0;
+  int rc = s2_problems(ctx, problems, n, &canon_metab, op, dp, &qsum);
+  if (rc) return rc;
+  std::unique_ptr<gmapdp_oligo_plan> plan;  // (views of the context's buffers: nothing to free)
+  rc = oligo_plan_build(ctx, op.data(), n, qseq_uc, qbytes, plan, true);
   if (rc) return rc;
   const size_t toff = plan->table_cap, doff = plan->diag_cap;
   hipStream_t s = ctx->stream;
@@ -3738,29 +3722,23 @@ extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem*
   if (e == hipSuccess) e = hipMemcpyAsync(ctx->s2probs.p, dp.data(), sizeof(DevStage2Problem) * n, hipMemcpyHostToDevice, s);
   // (onpos / omap are not cleared: the seeding writes every position of every call's slice first, and
   // the chaining reads nothing outside the slices)
-  if (e != hipSuccess) {
-    oligo_plan_free(plan);
-    return fail(ctx, GMAPDP_ENOMEM, "stage-2 buffers: %s", e);
-  }
-  rc = gmapdp_oligo_plan_run(ctx, plan, (const char*)ctx->qseq_uc.p, (gmapdp_oligo_result*)ctx->oresults.p,
+  if (e != hipSuccess) return fail(ctx, GMAPDP_ENOMEM, "stage-2 buffers: %s", e);
+  rc = gmapdp_oligo_plan_run(ctx, plan.get(), (const char*)ctx->qseq_uc.p, (gmapdp_oligo_result*)ctx->oresults.p,
                              (int32_t*)ctx->onpos.p, (int32_t*)ctx->omap.p, (uint32_t*)ctx->otable.p,
                              (int32_t*)ctx->odiag.p, nullptr);
   if (rc) {
     (void)ctx_sync(ctx, s);
-    oligo_plan_free(plan);
     return rc;
   }
   // the chaining scratch is sized exactly from the seeding (totalpositions, ndiagonals per call)
   std::vector<gmapdp_oligo_result> ores(n);
   e = hipMemcpyAsync(ores.data(), ctx->oresults.p, sizeof(gmapdp_oligo_result) * n, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = ctx_sync(ctx, s);
-  oligo_plan_free(plan);
   if (e != hipSuccess) return fail(ctx, GMAPDP_ELAUNCH, "stage-2 seeding: %s", e);
-  size_t scratch = 0, qsum = 0;
+  size_t scratch = 0;
   for (int i = 0; i < n; i++) {
     dp[i].scratch_offset = (int64_t)scratch;
     scratch += scratch_bytes_s2c(problems[i].querylength, ores[i].totalpositions, ores[i].ndiagonals);
-    qsum += (size_t)problems[i].querylength;
   }
   e = hipMemcpyAsync(ctx->s2probs.p, dp.data(), sizeof(DevStage2Problem) * n, hipMemcpyHostToDevice, s);
   if (e != hipSuccess) return fail(ctx, GMAPDP_ELAUNCH, "stage-2 descriptors: %s", e);
@@ -3789,17 +3767,10 @@ extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem*
       if (results[i].status == -3) return bad(ctx, "stage 2: chromosome positions past 2^31");
       overflow |= results[i].status == -2;
     }
-    if (!overflow) {
-      if (paths_needed) *paths_needed = (size_t)cnt[1];
-      if (pairs_needed) *pairs_needed = (size_t)cnt[2];
-      if (cnt[1] > path_cap || cnt[2] > pair_cap || (cnt[1] && !paths) || (cnt[2] && !pairs)) return GMAPDP_ESPACE;
-      if (cnt[1]) e = hipMemcpyAsync(paths, ctx->s2paths.p, sizeof(gmapdp_path) * cnt[1], hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess && cnt[2])
-        e = hipMemcpyAsync(pairs, ctx->s2pairs.p, sizeof(gmapdp_path_pair) * cnt[2], hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = ctx_sync(ctx, s);
-      if (e != hipSuccess) return fail(ctx, GMAPDP_ELAUNCH, "stage-2 copy-out: %s", e);
-      return GMAPDP_OK;
-    }
+    if (!overflow)  // (nothing overflowed: the counters are within the pools)
+      return s2_copy_out(ctx, s, (const gmapdp_path*)ctx->s2paths.p, (size_t)cnt[1],
+                         (const gmapdp_path_pair*)ctx->s2pairs.p, (size_t)cnt[2], paths, path_cap, pairs, pair_cap,
+                         paths_needed, pairs_needed, "stage-2 copy-out: %s");
     if (attempt >= 8) return fail(ctx, GMAPDP_ENOMEM, "stage-2 output pools keep overflowing%s", hipSuccess);
     pcap = std::max<size_t>(2 * pcap, (size_t)cnt[1] + 16);
     qcap = std::max<size_t>(2 * qcap, (size_t)cnt[2] + 64);
@@ -3810,13 +3781,17 @@ extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem*
 // Dynprog_microexon_int (dynprog_single.c:900): candidate search, then selection + pairs
 // (mx_kernel.hip).  Synchronous host-array batches.
 // ---------------------------------------------------------------------------
+// the problem's query slice lies within the query arena
+static bool mx_slice_ok(const gmapdp_microexon_problem& p, size_t qbytes) {
+  return p.rlength >= 0 && p.qoff >= 0 && (size_t)p.qoff + (size_t)p.rlength <= qbytes;
+}
+// pair records one call may write
+static size_t mx_pair_cap(const gmapdp_microexon_problem& p) { return (size_t)std::max(p.rlength, 0) + 2; }
+
 static int mx_upload(gmapdp_ctx* ctx, const gmapdp_microexon_problem* problems, int n, const char* qseq,
                      const char* qseq_uc, size_t qbytes) {
-  for (int i = 0; i < n; i++) {
-    const gmapdp_microexon_problem& p = problems[i];
-    if (p.rlength < 0 || p.qoff < 0 || (size_t)p.qoff + (size_t)p.rlength > qbytes)
-      return bad(ctx, "microexon: query slice outside the query arena");
-  }
+  for (int i = 0; i < n; i++)
+    if (!mx_slice_ok(problems[i], qbytes)) return bad(ctx, "microexon: query slice outside the query arena");
   hipStream_t s = ctx->stream;
   hipError_t e = ctx->mxprobs.ensure(sizeof(gmapdp_microexon_problem) * n);
   if (e == hipSuccess) e = ctx->mxres.ensure(sizeof(gmapdp_microexon_result) * n);
@@ -3832,7 +3807,7 @@ static int mx_upload(gmapdp_ctx* ctx, const gmapdp_microexon_problem* problems, 
 
 extern "C" size_t gmapdp_microexon_pair_capacity(const gmapdp_microexon_problem* problems, int n) {
   size_t c = 0;
-  for (int i = 0; i < n; i++) c += (size_t)std::max(problems[i].rlength, 0) + 2;
+  for (int i = 0; i < n; i++) c += mx_pair_cap(problems[i]);
   return c;
 }
 
@@ -3929,7 +3904,7 @@ extern "C" int gmapdp_microexon_finish(gmapdp_ctx* ctx, const gmapdp_microexon_p
                                                               (size_t)res[i].cand_offset + res[i].ncandidates > ncands)))
       return bad(ctx, "microexon: candidates outside the candidate array");
     res[i].pair_offset = (int64_t)poff;
-    poff += (size_t)std::max(problems[i].rlength, 0) + 2;
+    poff += mx_pair_cap(problems[i]);
   }
   if (poff > pair_capacity || !pairs) return bad(ctx, "microexon: pair arena too small");
   (void)hipSetDevice(ctx->device);
@@ -4043,34 +4018,27 @@ extern "C" int gmapdp_mixed_batch(gmapdp_ctx* ctx, const char* qseq, const char*
   }
   const int ndev = (int)plan.dev.size(), ngdev = (int)plan.gdev.size();
   // ---- microexon sections (as gmapdp_microexon_search / _finish) ----
-  for (int i = 0; i < nxs; i++) {
-    const gmapdp_microexon_problem& p = m->searches[i];
-    if (p.rlength < 0 || p.qoff < 0 || (size_t)p.qoff + (size_t)p.rlength > qbytes)
-      return bad(ctx, "microexon: query slice outside the query arena");
-  }
+  for (int i = 0; i < nxs; i++)
+    if (!mx_slice_ok(m->searches[i], qbytes)) return bad(ctx, "microexon: query slice outside the query arena");
   std::vector<gmapdp_microexon_result> fres(m->finish_results, m->finish_results + nxf);
   size_t fpoff = 0;
   for (int i = 0; i < nxf; i++) {
-    const gmapdp_microexon_problem& p = m->finishes[i];
-    if (p.rlength < 0 || p.qoff < 0 || (size_t)p.qoff + (size_t)p.rlength > qbytes)
-      return bad(ctx, "microexon: query slice outside the query arena");
+    if (!mx_slice_ok(m->finishes[i], qbytes)) return bad(ctx, "microexon: query slice outside the query arena");
     if (fres[i].ncandidates < 0 ||
         (fres[i].ncandidates > 0 && (fres[i].cand_offset < 0 ||
                                      (size_t)fres[i].cand_offset + fres[i].ncandidates > m->nfinish_candidates)))
       return bad(ctx, "microexon: candidates outside the candidate array");
     fres[i].pair_offset = (int64_t)fpoff;
-    fpoff += (size_t)std::max(p.rlength, 0) + 2;
+    fpoff += mx_pair_cap(m->finishes[i]);
   }
   if (nxf && (fpoff > m->finish_pair_capacity || !m->finish_pairs)) return bad(ctx, "microexon: pair arena too small");
   if (m->nfinish_candidates && !m->finish_candidates) return GMAPDP_EINVAL;
   std::vector<int64_t> wpoff(nxw);
   size_t wpairs = 0;
   for (int i = 0; i < nxw; i++) {
-    const gmapdp_microexon_problem& p = m->wholes[i];
-    if (p.rlength < 0 || p.qoff < 0 || (size_t)p.qoff + (size_t)p.rlength > qbytes)
-      return bad(ctx, "microexon: query slice outside the query arena");
+    if (!mx_slice_ok(m->wholes[i], qbytes)) return bad(ctx, "microexon: query slice outside the query arena");
     wpoff[i] = (int64_t)wpairs;
-    wpairs += (size_t)p.rlength + 2;
+    wpairs += mx_pair_cap(m->wholes[i]);  // (rlength >= 0 here)
   }
   if (nxw && (wpairs > m->whole_pair_capacity || !m->whole_pairs)) return bad(ctx, "microexon: whole-call pair arena too small");
   const bool fdev_me = nxf && !m->finish_probs;
@@ -4293,19 +4261,11 @@ extern "C" int gmapdp_mixed_batch(gmapdp_ctx* ctx, const char* qseq, const char*
 struct gmapdp_microexon_plan {
   int n = 0;
   size_t ncands = 0, npairs = 0;
-  gmapdp_microexon_problem* d_probs = nullptr;
-  int64_t* d_direct = nullptr;
-  int64_t* d_poff = nullptr;
-  gmapdp_microexon_candidate* d_cands = nullptr;
-  unsigned long long* d_counter = nullptr;
+  DevMem<gmapdp_microexon_problem> d_probs;
+  DevMem<int64_t> d_direct, d_poff;
+  DevMem<gmapdp_microexon_candidate> d_cands;
+  DevMem<unsigned long long> d_counter;
 };
-
-static void mx_plan_free(gmapdp_microexon_plan* P) {
-  if (!P) return;
-  for (void* b : {(void*)P->d_probs, (void*)P->d_direct, (void*)P->d_poff, (void*)P->d_cands, (void*)P->d_counter})
-    if (b) (void)hipFree(b);
-  delete P;
-}
 
 extern "C" int gmapdp_microexon_plan_create(gmapdp_ctx* ctx, const gmapdp_microexon_problem* problems, int n,
                                             const char* qseq, const char* qseq_uc, size_t qbytes,
@@ -4323,26 +4283,23 @@ extern "C" int gmapdp_microexon_plan_create(gmapdp_ctx* ctx, const gmapdp_microe
     direct[i] = (int64_t)c;
     c += (size_t)res[i].ncandidates;
     poff[i] = (int64_t)q;
-    q += (size_t)std::max(problems[i].rlength, 0) + 2;
+    q += mx_pair_cap(problems[i]);
   }
-  gmapdp_microexon_plan* P = new gmapdp_microexon_plan();
+  std::unique_ptr<gmapdp_microexon_plan> P(new gmapdp_microexon_plan());
   P->n = n;
   P->ncands = c;
   P->npairs = q;
-  hipError_t e = hipMalloc(&P->d_probs, sizeof(gmapdp_microexon_problem) * std::max(n, 1));
-  if (e == hipSuccess) e = hipMalloc(&P->d_direct, sizeof(int64_t) * std::max(n, 1));
-  if (e == hipSuccess) e = hipMalloc(&P->d_poff, sizeof(int64_t) * std::max(n, 1));
-  if (e == hipSuccess) e = hipMalloc(&P->d_cands, sizeof(gmapdp_microexon_candidate) * std::max<size_t>(c, 1));
-  if (e == hipSuccess) e = hipMalloc(&P->d_counter, sizeof(unsigned long long));
+  hipError_t e = P->d_probs.alloc(sizeof(gmapdp_microexon_problem) * std::max(n, 1));
+  if (e == hipSuccess) e = P->d_direct.alloc(sizeof(int64_t) * std::max(n, 1));
+  if (e == hipSuccess) e = P->d_poff.alloc(sizeof(int64_t) * std::max(n, 1));
+  if (e == hipSuccess) e = P->d_cands.alloc(sizeof(gmapdp_microexon_candidate) * std::max<size_t>(c, 1));
+  if (e == hipSuccess) e = P->d_counter.alloc(sizeof(unsigned long long));
   if (e == hipSuccess && n)
     e = hipMemcpy(P->d_probs, problems, sizeof(gmapdp_microexon_problem) * n, hipMemcpyHostToDevice);
   if (e == hipSuccess && n) e = hipMemcpy(P->d_direct, direct.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice);
   if (e == hipSuccess && n) e = hipMemcpy(P->d_poff, poff.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    mx_plan_free(P);
-    return fail(ctx, GMAPDP_ENOMEM, "microexon plan: %s", e);
-  }
-  *plan = P;
+  if (e != hipSuccess) return fail(ctx, GMAPDP_ENOMEM, "microexon plan: %s", e);
+  *plan = P.release();
   return GMAPDP_OK;
 }
 
@@ -4362,7 +4319,7 @@ extern "C" int gmapdp_microexon_plan_run(gmapdp_ctx* ctx, const gmapdp_microexon
   // d_cand_probs NULL: the finish evaluates the candidates' MaxEnt sites on the device
   const double* metab = nullptr;
   if ((what & 2) && !d_cand_probs && !(metab = me_tables(ctx))) return GMAPDP_EINVAL;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   hipError_t e = hipSuccess;
   if (what & 1)
     e = launch_mx_search(plan->n, s, plan->d_probs, ctx->d_genome, ctx->genome_words, d_qseq, d_qseq_uc,
@@ -4378,7 +4335,7 @@ extern "C" const gmapdp_microexon_candidate* gmapdp_microexon_plan_device_candid
   return plan ? plan->d_cands : nullptr;
 }
 
-extern "C" void gmapdp_microexon_plan_destroy(gmapdp_microexon_plan* plan) { mx_plan_free(plan); }
+extern "C" void gmapdp_microexon_plan_destroy(gmapdp_microexon_plan* plan) { delete plan; }
 
 // Test instrumentation: the chaining scratch of the last gmapdp_stage2_batch (its layout is
 // s2_scratch in s2c_kernel.hip; for a one-problem batch it starts at byte 0).
@@ -4402,28 +4359,21 @@ extern "C" int gmapdp_debug_canon_counters(gmapdp_ctx* ctx, unsigned long long* 
 // ---------------------------------------------------------------------------
 struct gmapdp_stage2_plan {
   int n = 0;
-  gmapdp_oligo_plan* oplan = nullptr;
-  DevStage2Problem* d_probs = nullptr;
-  gmapdp_oligo_result* d_ores = nullptr;
-  int32_t *d_npos = nullptr, *d_map = nullptr, *d_diag = nullptr;
-  uint32_t* d_table = nullptr;
-  unsigned char* d_scratch = nullptr;
-  unsigned long long* d_counters = nullptr;
-  gmapdp_path* d_paths = nullptr;
-  gmapdp_path_pair* d_pairs = nullptr;
+  std::unique_ptr<gmapdp_oligo_plan> oplan;
+  DevMem<DevStage2Problem> d_probs;
+  DevMem<gmapdp_oligo_result> d_ores;
+  DevMem<int32_t> d_npos, d_map;
+  // the seeding's arenas: views of the context's grow-only otable / odiag during the sizing run (upper bounds,
+  // tens of GB), then the plan's own allocations of the measured sizes
+  DevMem<uint32_t> d_table;
+  DevMem<int32_t> d_diag;
+  DevMem<unsigned char> d_scratch;
+  DevMem<unsigned long long> d_counters;
+  DevMem<gmapdp_path> d_paths;
+  DevMem<gmapdp_path_pair> d_pairs;
   size_t qbytes = 0, scratch = 0, path_cap = 0, pair_cap = 0;
   const double* d_canon = nullptr;  // GMAPDP_S2_CANONICAL_MIDDLE: the MaxEnt tables of the sweep's canonical variant
 };
-
-static void stage2_plan_free(gmapdp_stage2_plan* p) {
-  if (!p) return;
-  oligo_plan_free(p->oplan);
-  void* bufs[] = {p->d_probs, p->d_ores, p->d_npos, p->d_map, p->d_diag, p->d_table, p->d_scratch, p->d_counters,
-                  p->d_paths, p->d_pairs};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  delete p;
-}
 
 static int stage2_plan_launch(gmapdp_ctx* ctx, const gmapdp_stage2_plan* P, const char* d_qseq, const char* d_qseq_uc,
                               gmapdp_stage2_result* d_results, hipStream_t s, bool seed, int chain) {
@@ -4432,7 +4382,7 @@ static int stage2_plan_launch(gmapdp_ctx* ctx, const gmapdp_stage2_plan* P, cons
   if (seed) {
     // (no clearing of d_npos / d_map: the seeding kernels write npositions 0 and the 8-mer of every query
     // position of every call before anything reads them, and nothing reads outside the calls' slices)
-    int rc = gmapdp_oligo_plan_run(ctx, P->oplan, d_qseq_uc, P->d_ores, P->d_npos, P->d_map, P->d_table, P->d_diag, s);
+    int rc = gmapdp_oligo_plan_run(ctx, P->oplan.get(), d_qseq_uc, P->d_ores, P->d_npos, P->d_map, P->d_table, P->d_diag, s);
     if (rc) return rc;
   }
   if (chain) {  // phases: 1 s2a, 2 s2b, 4 s2c (the pools restart with s2a or s2c)
@@ -4456,59 +4406,39 @@ int gmapdp_stage2_plan_create(gmapdp_ctx* ctx, const gmapdp_stage2_problem* prob
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   (void)hipSetDevice(ctx->device);
   const double* canon_metab = nullptr;
-  if (int frc = s2_batch_flags(ctx, problems, n, &canon_metab)) return frc;
-  std::vector<gmapdp_oligo_problem> op(n);
-  std::vector<DevStage2Problem> dp(n);
+  std::vector<gmapdp_oligo_problem> op;
+  std::vector<DevStage2Problem> dp;
   size_t qsum = 0;
-  for (int i = 0; i < n; i++) {
-    const gmapdp_stage2_problem& p = problems[i];
-    if (p.maxintronlen < 0) return bad(ctx, "stage 2: negative maxintronlen");
-    op[i] = gmapdp_oligo_problem{p.qoff, p.querylength, p.chrstart, p.chrend, p.chroffset, p.chrhigh,
-                                 p.plusp ? 1 : 0, 0};
-    dp[i] = DevStage2Problem{p.qoff, p.querylength, p.chrstart, p.chrend, p.chroffset, p.chrhigh, p.plusp ? 1 : 0,
-                             p.splicingp ? 1 : 0, (uint32_t)p.maxintronlen, i, 0};
-    qsum += (size_t)p.querylength;
-  }
-  gmapdp_stage2_plan* P = new gmapdp_stage2_plan();
+  int rc = s2_problems(ctx, problems, n, &canon_metab, op, dp, &qsum);
+  if (rc) return rc;
+  std::unique_ptr<gmapdp_stage2_plan> P(new gmapdp_stage2_plan());
   PlanTimer tm("stage2_plan_create");
   P->n = n;
   P->qbytes = qbytes;
   P->d_canon = canon_metab;
-  int rc = oligo_plan_build(ctx, op.data(), n, qseq_uc, qbytes, &P->oplan, false, /*sizing*/ true);
+  rc = oligo_plan_build(ctx, op.data(), n, qseq_uc, qbytes, P->oplan, false, /*sizing*/ true);
   tm.mark("oligo_plan_build");
-  if (rc) {
-    delete P;
-    return rc;
-  }
+  if (rc) return rc;
   const size_t toff = P->oplan->table_cap, doff = P->oplan->diag_cap;
-  hipError_t e = hipMalloc(&P->d_probs, sizeof(DevStage2Problem) * n);
-  if (e == hipSuccess) e = hipMalloc(&P->d_ores, sizeof(gmapdp_oligo_result) * n);
-  if (e == hipSuccess) e = hipMalloc(&P->d_npos, sizeof(int32_t) * qbytes);
-  if (e == hipSuccess) e = hipMalloc(&P->d_map, sizeof(int32_t) * qbytes);
-  // the sizing run's upper-bound arenas: the context's grow-only buffers (see gmapdp_oligo_plan::borrowed)
-  auto drop_sizing = [&]() {
-    P->d_table = nullptr;
-    P->d_diag = nullptr;
-    P->oplan->d_nhits = nullptr;
-  };
+  hipError_t e = P->d_probs.alloc(sizeof(DevStage2Problem) * n);
+  if (e == hipSuccess) e = P->d_ores.alloc(sizeof(gmapdp_oligo_result) * n);
+  if (e == hipSuccess) e = P->d_npos.alloc(sizeof(int32_t) * qbytes);
+  if (e == hipSuccess) e = P->d_map.alloc(sizeof(int32_t) * qbytes);
+  // the sizing run's upper-bound arenas: views of the context's grow-only buffers
   if (e == hipSuccess) e = ctx->otable.ensure(sizeof(uint32_t) * std::max<size_t>(toff, 1), true);
   if (e == hipSuccess) e = ctx->odiag.ensure(4 * sizeof(int32_t) * std::max<size_t>(doff, 1), true);
   if (e == hipSuccess) e = ctx->onhits.ensure(sizeof(int32_t) * n);
-  P->d_table = (uint32_t*)ctx->otable.p;
-  P->d_diag = (int32_t*)ctx->odiag.p;
-  P->oplan->d_nhits = (int32_t*)ctx->onhits.p;
-  if (e == hipSuccess) e = hipMalloc(&P->d_counters, s2_counters_bytes(n));
+  P->d_table.view((uint32_t*)ctx->otable.p);
+  P->d_diag.view((int32_t*)ctx->odiag.p);
+  P->oplan->d_nhits.view((int32_t*)ctx->onhits.p);
+  if (e == hipSuccess) e = P->d_counters.alloc(s2_counters_bytes(n));
   if (e == hipSuccess) e = hipMemcpy(P->d_probs, dp.data(), sizeof(DevStage2Problem) * n, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = ctx->qseq_uc.ensure(qbytes);
   if (e == hipSuccess) e = hipMemcpy(ctx->qseq_uc.p, qseq_uc, qbytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    drop_sizing();
-    stage2_plan_free(P);
-    return fail(ctx, GMAPDP_ENOMEM, "stage-2 plan: %s", e);
-  }
+  if (e != hipSuccess) return fail(ctx, GMAPDP_ENOMEM, "stage-2 plan: %s", e);
   tm.mark("buffers");
   // size the chaining scratch from one seeding run
-  rc = stage2_plan_launch(ctx, P, nullptr, (const char*)ctx->qseq_uc.p, nullptr, ctx->stream, true, 0);
+  rc = stage2_plan_launch(ctx, P.get(), nullptr, (const char*)ctx->qseq_uc.p, nullptr, ctx->stream, true, 0);
   std::vector<gmapdp_oligo_result> ores(n);
   std::vector<int32_t> nhits(n);
   if (!rc) {
@@ -4518,23 +4448,16 @@ int gmapdp_stage2_plan_create(gmapdp_ctx* ctx, const gmapdp_stage2_problem* prob
     if (e == hipSuccess) e = ctx_sync(ctx, ctx->stream);
     if (e != hipSuccess) rc = fail(ctx, GMAPDP_ELAUNCH, "stage-2 plan seeding: %s", e);
   }
-  drop_sizing();
-  if (rc) {
-    stage2_plan_free(P);
-    return rc;
-  }
+  if (rc) return rc;
   tm.mark("sizing_run");
   // The seeding's arenas were sized from upper bounds (a window's worth of positions and 24 diagonals per
   // query position: 19 GB for 10 000 5-kb reads).  Re-lay them out from this run's measured use
   // (oligo_plan_relayout) so the plan keeps only what its runs write.
-  e = oligo_plan_relayout(ctx, P->oplan, op.data(), ores.data(), nhits.data());
+  e = oligo_plan_relayout(ctx, P->oplan.get(), op.data(), ores.data(), nhits.data());
   tm.mark("relayout");
-  if (e == hipSuccess) e = hipMalloc(&P->d_table, sizeof(uint32_t) * std::max<size_t>(P->oplan->table_cap, 1));
-  if (e == hipSuccess) e = hipMalloc(&P->d_diag, 4 * sizeof(int32_t) * std::max<size_t>(P->oplan->diag_cap, 1));
-  if (e != hipSuccess) {
-    stage2_plan_free(P);
-    return fail(ctx, GMAPDP_ENOMEM, "stage-2 plan arenas: %s", e);
-  }
+  if (e == hipSuccess) e = P->d_table.alloc(sizeof(uint32_t) * std::max<size_t>(P->oplan->table_cap, 1));
+  if (e == hipSuccess) e = P->d_diag.alloc(4 * sizeof(int32_t) * std::max<size_t>(P->oplan->diag_cap, 1));
+  if (e != hipSuccess) return fail(ctx, GMAPDP_ENOMEM, "stage-2 plan arenas: %s", e);
   for (int i = 0; i < n; i++) {
     dp[i].scratch_offset = (int64_t)P->scratch;
     // (a call whose sizing run overflowed its event pool measured no diagonals: its arena's upper bound)
@@ -4544,16 +4467,13 @@ int gmapdp_stage2_plan_create(gmapdp_ctx* ctx, const gmapdp_stage2_problem* prob
   }
   P->path_cap = 16 + 4 * (size_t)n;
   P->pair_cap = 64 + 3 * qsum;
-  e = hipMalloc(&P->d_scratch, std::max<size_t>(P->scratch, 256));
+  e = P->d_scratch.alloc(std::max<size_t>(P->scratch, 256));
   if (e == hipSuccess) e = hipMemcpy(P->d_probs, dp.data(), sizeof(DevStage2Problem) * n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&P->d_paths, sizeof(gmapdp_path) * P->path_cap);
-  if (e == hipSuccess) e = hipMalloc(&P->d_pairs, sizeof(gmapdp_path_pair) * P->pair_cap);
+  if (e == hipSuccess) e = P->d_paths.alloc(sizeof(gmapdp_path) * P->path_cap);
+  if (e == hipSuccess) e = P->d_pairs.alloc(sizeof(gmapdp_path_pair) * P->pair_cap);
   tm.mark("pools");
-  if (e != hipSuccess) {
-    stage2_plan_free(P);
-    return fail(ctx, GMAPDP_ENOMEM, "stage-2 plan pools: %s", e);
-  }
-  *plan = P;
+  if (e != hipSuccess) return fail(ctx, GMAPDP_ENOMEM, "stage-2 plan pools: %s", e);
+  *plan = P.release();
   return GMAPDP_OK;
 }
 
@@ -4565,15 +4485,14 @@ int gmapdp_stage2_plan_run(gmapdp_ctx* ctx, const gmapdp_stage2_plan* plan, cons
   (void)hipSetDevice(ctx->device);
   // what: 1 seeding, 2 chaining; or one chaining kernel alone over a previous run's scratch: 4 s2a, 8 s2b, 16 s2c
   const int chain = (what & 2) ? 7 : ((what >> 2) & 7);
-  return stage2_plan_launch(ctx, plan, d_qseq, d_qseq_uc, d_results, stream ? (hipStream_t)stream : ctx->stream,
-                            (what & 1) != 0, chain);
+  return stage2_plan_launch(ctx, plan, d_qseq, d_qseq_uc, d_results, stream_of(ctx, stream), (what & 1) != 0, chain);
 }
 
 int gmapdp_stage2_plan_seeding_results(gmapdp_ctx* ctx, const gmapdp_stage2_plan* plan, void* stream,
                                        gmapdp_oligo_result* out) {
   if (!ctx || !plan || !out) return GMAPDP_EINVAL;
   (void)hipSetDevice(ctx->device);
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   hipError_t e = hipMemcpyAsync(out, plan->d_ores, sizeof(gmapdp_oligo_result) * plan->n, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = ctx_sync(ctx, s);
   return e == hipSuccess ? GMAPDP_OK : fail(ctx, GMAPDP_ELAUNCH, "stage-2 seeding results: %s", e);
@@ -4596,22 +4515,16 @@ int gmapdp_stage2_plan_fetch(gmapdp_ctx* ctx, const gmapdp_stage2_plan* plan, co
   if (paths_needed) *paths_needed = 0;
   if (pairs_needed) *pairs_needed = 0;
   (void)hipSetDevice(ctx->device);
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   unsigned long long cnt[4] = {0, 0, 0, 0};
   hipError_t e = hipMemcpyAsync(results, d_results, sizeof(gmapdp_stage2_result) * plan->n, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipMemcpyAsync(cnt, plan->d_counters, sizeof(cnt), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = ctx_sync(ctx, s);
   if (e != hipSuccess) return fail(ctx, GMAPDP_ELAUNCH, "stage-2 plan fetch: %s", e);
   // the pools' atomics count past their capacity when calls overflow (those report status -2)
-  const size_t np = std::min<size_t>(cnt[1], plan->path_cap), nq = std::min<size_t>(cnt[2], plan->pair_cap);
-  if (paths_needed) *paths_needed = np;
-  if (pairs_needed) *pairs_needed = nq;
-  if (np > path_cap || nq > pair_cap || (np && !paths) || (nq && !pairs)) return GMAPDP_ESPACE;
-  if (np) e = hipMemcpyAsync(paths, plan->d_paths, sizeof(gmapdp_path) * np, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess && nq) e = hipMemcpyAsync(pairs, plan->d_pairs, sizeof(gmapdp_path_pair) * nq, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = ctx_sync(ctx, s);
-  if (e != hipSuccess) return fail(ctx, GMAPDP_ELAUNCH, "stage-2 plan fetch: %s", e);
-  return GMAPDP_OK;
+  return s2_copy_out(ctx, s, plan->d_paths, std::min<size_t>(cnt[1], plan->path_cap), plan->d_pairs,
+                     std::min<size_t>(cnt[2], plan->pair_cap), paths, path_cap, pairs, pair_cap, paths_needed,
+                     pairs_needed, "stage-2 plan fetch: %s");
 }
 
 // The compact stream of the plan's path pairs (pc_kernel.hip), one list per path record of the pool
@@ -4635,6 +4548,6 @@ int gmapdp_stage2_plan_seeding_classes(const gmapdp_stage2_plan* plan, int* n16,
   return GMAPDP_OK;
 }
 
-void gmapdp_stage2_plan_destroy(gmapdp_stage2_plan* plan) { stage2_plan_free(plan); }
+void gmapdp_stage2_plan_destroy(gmapdp_stage2_plan* plan) { delete plan; }
 
 }  // extern "C"

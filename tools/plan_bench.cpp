@@ -1,7 +1,8 @@
 // tools/plan_bench.cpp -- host-only timing of the DP plan build (build_plan: per-problem prologues and launch
 // classification) on a dumped block of descriptors; no GPU is touched.  Diagnostic, not the product:
-//   make -C gmap-2024_amd && hipcc -O3 -std=c++17 -o /tmp/plan_bench tools/plan_bench.cpp \
-//       gmap-2024_amd/build/{dp,ux,cg,oi,s2c,mx,sj,me}_kernel.hip.o
+//   make -C gmap-2024_amd && hipcc -O3 -std=c++17 --offload-arch=gfx950 -c tools/plan_bench.cpp -o /tmp/plan_bench.o && \
+//       hipcc --offload-arch=gfx950 -o /tmp/plan_bench /tmp/plan_bench.o \
+//       gmap-2024_amd/build/{dp,ux,cg,oi,s2scan,s2c,mx,sj,me,pc}_kernel.hip.o
 //   /tmp/plan_bench <dir with single.bin end.bin genome.bin> [reps]
 #include "../gmap-2024_amd/csrc/gmapdp_engine.cpp"
 
