@@ -877,6 +877,180 @@ __device__ __forceinline__ void traceback_band(int lane, const WORD* dirs, int W
   traceback_walk(lane, d, r, c, G, q, quc, gch, cons, watson, chroffset, chrhigh, blocks, nwords, out, t);
 }
 
+// ---- row-held fill of the genome-gap kernel: a lane keeps one query row for a stretch of T columns ----
+// fill_band binds a lane to a band offset, so a lane changes its row every column and whatever belongs
+// to a row (E, the carried bridge candidate, the score word, the other side's dinucleotide code and
+// probability, the candidate's column limit) is shifted or fetched again each column.  Here, for the
+// columns c in [mT + 1, mT + T], lane l holds row base_m + l with base_m = mT + 1 - uband: the band rows
+// [c - uband, c + lband] lie in lanes [c - 1 - mT, c - 1 - mT + W - 1], inside the wave when
+// T + W - 1 <= 64.  Within a stretch nothing row-bound moves: E, the left H and the candidate stay in
+// the lane, the row's constants are loaded once, the diagonal H comes from the lane below (DPP) and the
+// F chain is the plain wave scan (rows ascend with lanes, no wrap).  Every T columns the rows that have
+// left the band store their Part / diag entries together and the state moves down T lanes
+// (ds_bpermute).  The row above the new lane 0 is still the diagonal input of the stretch's first
+// column: its H is parked in lane 63, which is never a band row in that column, and the diagonal is
+// taken with wave_ror:1.  Direction planes: the four ballots per column as fill_band<1> stores them,
+// bit l being row base_m + l, i.e. bit k + (c - 1) % T for band offset k (StretchDirs).
+// One-word bands (R = 1), whole wave, bridge carry, directions in global scratch, no endpoint search.
+__host__ __device__ inline int gg_stretch(int W) { return W <= 49 ? 16 : W <= 57 ? 8 : W <= 61 ? 4 : 0; }
+
+__device__ __forceinline__ int dpp_wave_ror1(int x) {
+  // lane i <- lane i-1; lane 0 <- lane 63
+  return __builtin_amdgcn_update_dpp(x, x, 0x13C, 0xf, 0xf, false);
+}
+
+__device__ __forceinline__ void fill_stretch(int lane, int T, int rlen, int glen, int lband, int uband, int open,
+                                             int ext, int late, const int32_t* scw, const uint8_t* gcl,
+                                             uint64_t* dirs, const BridgeCarry& B) {
+  const int sat = kNegInf32;
+  int r = 1 - uband + lane;  // the lane's row in this stretch
+  int Hs, E = kNegInf32;
+  {  // column 0 (dynprog.c:1331-1369); lane 63 parks row -uband, the diagonal of lane 0's row in column 1
+    const int r0 = (lane == 63) ? -uband : r;
+    Hs = kNegInf32;
+    if (r0 >= 0 && r0 <= rlen) Hs = (r0 == 0) ? 0 : (r0 <= lband ? open + r0 * ext : kNegInf32);
+  }
+  // carried bridge candidate of the row (score, column + 1 (0: none), probability) and matrix[r][r]
+  int cs = 0, cc = 0, dcap = 0;
+  double cp = 0.0;
+  // per-row constants of the stretch
+  int scv, rext = r * ext, rdi, climit;
+  double rp;
+  auto row_constants = [&]() __attribute__((always_inline)) {
+    scv = scw[min((unsigned)r, (unsigned)(rlen + 1))];  // (a row outside [0, rlen + 1] is never a valid cell)
+    const bool inrow = (r >= 1) & (r <= rlen - 1);
+    const int other = inrow ? rlen - r : 0;
+    rdi = B.rowdi[other];
+    rp = B.rowp[other];
+    // a cell is a candidate when it is valid, 1 <= r <= rlength - 1, and c <= glength - 2, c < rdist - other,
+    // c < r + uband (band offset >= 1): one limit per row
+    climit = inrow ? min(min(glen - 2, B.rdist - other - 1), r + uband - 1) : -1;
+  };
+  // rows leaving the wave: the candidate is final once the row has passed band offset 0 (or the fill has
+  // ended), matrix[r][r] was captured at column r
+  auto retire = [&](bool leaving) __attribute__((always_inline)) {
+    if (leaving && r >= 1 && r <= rlen - 1) {
+      if (r <= glen + lband) {  // (a row below every column's band holds no candidate: left unwritten)
+        int4 v;
+        const int2 pw = *reinterpret_cast<const int2*>(&cp);
+        v.x = pw.x;
+        v.y = pw.y;
+        v.z = cs;
+        v.w = cc - 1;
+        *reinterpret_cast<int4*>(&B.part[r]) = v;
+      }
+      if (r <= glen) B.diag[r] = dcap;
+    }
+  };
+  row_constants();
+  const int text = T * ext;
+  int rtop_ext = -uband * ext;  // (c - uband) * ext, advanced by ext per column
+  int oce = open;               // open + c * ext
+  for (int c0 = 0; c0 < glen; c0 += T) {
+    if (c0 > 0) {  // re-base: rows [base, base + T) have left the band; every other row moves down T lanes
+      retire(lane < T);
+      const bool enter = lane >= 64 - T;  // rows entering the wave: -infinity / zero defaults
+      const int src = (lane + T) << 2;
+      // lane 63 parks the H of the row above the new lane 0 (band offset 0 of the column just filled)
+      const int hv = __builtin_amdgcn_ds_bpermute(lane == 63 ? (T - 1) << 2 : src, Hs);
+      Hs = (enter & (lane != 63)) ? kNegInf32 : hv;
+      const int ev = __builtin_amdgcn_ds_bpermute(src, E);
+      E = enter ? kNegInf32 : ev;
+      const int csv = __builtin_amdgcn_ds_bpermute(src, cs);
+      cs = enter ? 0 : csv;
+      const int ccv = __builtin_amdgcn_ds_bpermute(src, cc);
+      cc = enter ? 0 : ccv;
+      const int dv = __builtin_amdgcn_ds_bpermute(src, dcap);
+      dcap = enter ? 0 : dv;
+      const int2 pw = *reinterpret_cast<const int2*>(&cp);
+      int2 qw;
+      qw.x = __builtin_amdgcn_ds_bpermute(src, pw.x);
+      qw.y = __builtin_amdgcn_ds_bpermute(src, pw.y);
+      if (enter) qw.x = qw.y = 0;
+      cp = *reinterpret_cast<const double*>(&qw);
+      r += T;
+      rext += text;
+      row_constants();
+    }
+    const int cend = min(c0 + T, glen);
+    for (int c = c0 + 1; c <= cend; c++) {
+      const int gi4 = __builtin_amdgcn_readfirstlane(gcl[c]) << 2;  // bit offset of the class in the score word
+      const int rtop = c - uband;
+      const int rlo = rtop < 1 ? 1 : rtop;
+      const int rhigh = (c + lband) < rlen ? (c + lband) : rlen;
+      rtop_ext += ext;
+      oce += ext;
+      // last_nogap entering row rlo (dynprog.c:1411-1449)
+      const int L0 = (c == 1) ? (kNegInf32 - open + 1) : (c <= uband ? oce : kNegInf32);
+      const int row0 = (c <= uband) ? oce : kNegInf32;  // row 0 of this column (dynprog.c:1318-1325)
+      const bool valid = (r >= rlo) & (r <= rhigh);
+      const int s = __builtin_amdgcn_sbfe(scv, gi4, 4);
+      const int Hd = dpp_wave_ror1(Hs);  // (r - 1, c - 1)
+      // Egap (dynprog.c:1518-1524): the same row, one column back
+      const int es = Hs + open;
+      const bool eb = E > es - late;
+      const int En = max(E, es) + ext;
+      const int dg = Hd + s;
+      const bool hb = En > dg - late;
+      const int Hp = max(En, dg);
+      // F chain: F(r) = r*ext + max(init, max_{rlo<=j<r} (H'(j) + open - j*ext))
+      const int A = valid ? Hp + open - rext : kSent;
+      const int X = dpp_wave_shr1(wave_scan_max(A), kSent);
+      const int init = max(kNegInf32, L0 + open) - ((rtop > 1) ? rtop_ext - ext : 0);  // (rlo - 1) * ext
+      const int F = rext + max(init, X);
+      const bool vb = F > Hp - late;
+      const int Hun = max(F, Hp);
+      const bool fb = F > Hun + open - late;  // Fgap of the cell below, stored with this cell (fill_band)
+      const uint64_t mvalid = ballot(valid);
+      const uint64_t mV = ballot(vb) & mvalid;
+      const uint64_t mH = ballot(hb) & ~mV & mvalid;
+      const uint64_t mE = ballot(eb) & mvalid;
+      const uint64_t mF = ballot(fb) & mvalid;
+      const int Hc = max(Hun, sat);
+      // (band offset 0 keeps its unclamped value: its only reader is the next band-top cell's diagonal)
+      Hs = valid ? ((r == rtop) ? Hun : Hc) : ((r == 0) ? row0 : kNegInf32);
+      E = valid ? En : kNegInf32;
+      {  // bridge candidate of the row, updated in place
+        const int cdi = __builtin_amdgcn_readfirstlane(B.coldi[c]);
+        const double cpc = B.colp[c];
+        const bool cand = valid & (c <= climit);
+        const int s2 = B.isc[rdi & cdi] + Hc;
+        const double p = rp + cpc;
+        const bool take = cand & ((cc == 0) | (s2 > cs) | ((s2 == cs) & (p > cp)));
+        cs = take ? s2 : cs;
+        cc = take ? c + 1 : cc;
+        cp = take ? p : cp;
+        dcap = (r == c) ? Hc : dcap;  // matrix[r][r]
+      }
+#ifndef GMAPDP_GGX_NODIRS  // (timing experiment, make variant: the genome-gap fills store no directions)
+      if (lane == 0) {
+        uint64_t* dcol = dirs + (size_t)c * 4;
+        dcol[0] = mH;
+        dcol[1] = mV;
+        dcol[2] = mE;
+        dcol[3] = mF;
+      }
+#else
+      (void)mH, (void)mE, (void)mF;
+#endif
+    }
+  }
+  retire(true);  // the rows still in the wave after the last column
+}
+
+// direction bits of a one-word genome-gap fill in global scratch: band offset k at bit k + (c - 1) % T of the
+// column's words for fill_stretch (tmask = T - 1), at bit k for fill_band<1> (tmask = 0, as BandDirs<1>)
+struct StretchDirs {
+  const uint64_t* dirs;
+  int W, uband, tmask;
+  __device__ uint32_t operator()(int c, int t, int r) const {
+    int k = r - c + uband;
+    if (k < 0 || k >= W || c < 1) return 0u;  // outside the band: cleared to DIAG (dynprog.c:498)
+    if (t == 3 && --k < 0) return 0u;         // Fgap of (r, c) is stored with the cell above it
+    return (uint32_t)(dirs[(size_t)c * 4 + t] >> (k + ((c - 1) & tmask))) & 1u;
+  }
+};
+
 // Genome skip whose characters come from the problem's own genome string (Pairpool_add_genomeskip with a
 // genomesequence, pairpool.c:1145-1154): column cc's character is gch[cc].
 template <typename GV>

@@ -920,10 +920,27 @@ __global__ __launch_bounds__(128) GGX_ATTR void gg_kernel(
 
   // ---- 2. fills, concurrently: wave 0 R (feeds the B candidates), wave 1 L (the C candidates) ----
   const int rdist = P.rev_goffsetR - P.goffsetL;  // "cR < rightoffset - leftoffset - cL"
-  {
+  // One-word bands with their directions in global scratch take the row-held fill (fill_stretch) when the
+  // band leaves room for a stretch of T >= 4 columns in the wave and the plan asks for it (kGRowFill): a
+  // wave-uniform choice per fill, a function of the band width alone, which the traceback repeats.
+  int TL = 0, TR = 0;
+  if constexpr (R == 1 && !DPK) {
+    if (flags & kGRowFill) {
+      TL = gg_stretch(WL);
+      TR = gg_stretch(WR);
+    }
+  }
+  const int Tw = wave == 0 ? TR : TL;
+  if (R == 1 && !DPK && Tw) {
+    const bool w0 = wave == 0;
+    const BridgeCarry B{w0 ? ldi : rdi, w0 ? rdi : ldi, w0 ? pL : pR, w0 ? pR : pL, isc, rdist,
+                        w0 ? partB : partC, w0 ? diagR : diagL};
+    fill_stretch(lane, Tw, rlen, w0 ? gR : gL, lband, w0 ? ubandR : ubandL, P.open, P.extend, w0 ? 1 - late : late,
+                 w0 ? scR : scL, w0 ? gclR : gclL, w0 ? dirsR : dirsL, B);
+  } else {
     int br, bc;
-    // (a band narrower than the wave's 64 R elements -- every bench genome gap: 37 -- takes the narrow-band
-    // shifts; a wave-uniform choice per fill)
+    // (a band narrower than the wave's 64 R elements takes the narrow-band shifts; a wave-uniform choice
+    // per fill)
     if (wave == 0) {
       const BridgeCarry B{ldi, rdi, pL, pR, isc, rdist, partB, diagR};
       if (WR < 64 * R)
@@ -1063,6 +1080,10 @@ __global__ __launch_bounds__(128) GGX_ATTR void gg_kernel(
     const PackedDirs dR{lo, lo + 4 * (gR + 1), WR, ubandR, gg_dir_nhigh(WR)};
     traceback_walk(lane, dR, bestrR, bestcR, GR, qR, qucR, gchR, cons, watson, P.chroffset, P.chrhigh, blocks, nwords,
                    out, t);
+  } else if constexpr (R == 1) {  // fill_stretch's bit positions, or fill_band<1>'s (TR = 0)
+    const StretchDirs dR{dirsR, WR, ubandR, TR ? TR - 1 : 0};
+    traceback_walk(lane, dR, bestrR, bestcR, GR, qR, qucR, gchR, cons, watson, P.chroffset, P.chrhigh, blocks, nwords,
+                   out, t);
   } else {
     traceback_band<R>(lane, dirsR, WR, ubandR, bestrR, bestcR, GR, qR, qucR, gchR, cons, watson, P.chroffset,
                       P.chrhigh, blocks, nwords, out, t);
@@ -1076,6 +1097,10 @@ __global__ __launch_bounds__(128) GGX_ATTR void gg_kernel(
   if constexpr (DPK) {
     const uint32_t* lo = reinterpret_cast<const uint32_t*>(dirsL);
     const PackedDirs dL{lo, lo + 4 * (gL + 1), WL, ubandL, gg_dir_nhigh(WL)};
+    traceback_walk(lane, dL, bestrL, bestcL, GL, qL, qucL, gchL, cons, watson, P.chroffset, P.chrhigh, blocks, nwords,
+                   out, t);
+  } else if constexpr (R == 1) {
+    const StretchDirs dL{dirsL, WL, ubandL, TL ? TL - 1 : 0};
     traceback_walk(lane, dL, bestrL, bestcL, GL, qL, qucL, gchL, cons, watson, P.chroffset, P.chrhigh, blocks, nwords,
                    out, t);
   } else {

@@ -938,6 +938,9 @@ static size_t env_size(const char* name, size_t dflt) {
 // they always go to the L2-resident scratch, which measured fastest (more problems per CU).
 // GMAPDP_GG_LDS_DIRS_MAX overrides it, for experiments.
 static size_t gg_lds_dirs_max() { return env_size("GMAPDP_GG_LDS_DIRS_MAX", 0); }
+// GMAPDP_GG_ROWFILL=0 keeps every genome-gap fill in the band-lane layout (A/B runs, tests); by default
+// one-word bands with global direction planes take the row-held fill (fill_stretch, dp_device.h)
+static bool gg_rowfill() { return env_size("GMAPDP_GG_ROWFILL", 1) != 0; }
 // GMAPDP_DP_ROWS=0 keeps every single / end gap in the band layout (experiments, tests)
 static bool rows_disabled() {
   static const bool v = env_size("GMAPDP_DP_ROWS", 1) == 0;
@@ -1474,7 +1477,7 @@ static ClassOf classify_dev(DevProblem& d, bool latency) {
 }
 
 // one genome gap's launch class
-static ClassOf classify_gdev(DevGenomeProblem& d, bool latency, size_t lds_dirs_max) {
+static ClassOf classify_gdev(DevGenomeProblem& d, bool latency, size_t lds_dirs_max, bool rowfill) {
   ClassOf c{};
   // traceback R (<= r + gR records) + gap holder + traceback L (<= r + gL records)
   c.pair = 2 * (size_t)d.rlength + (size_t)d.glengthL + (size_t)d.glengthR + 4;
@@ -1496,6 +1499,8 @@ static ClassOf classify_gdev(DevGenomeProblem& d, bool latency, size_t lds_dirs_
   if (R > kMaxR) { c.err = "band wider than 4096"; return c; }
   size_t lds = lds_bytes_gg(d.rlength, d.glengthL, d.glengthR, R, true, std::max(WL, WR));
   const bool dirs_lds = lds <= lds_dirs_max;
+  // (the kernel picks the stretch per side from the band width; LDS-packed planes keep fill_band)
+  d.flags = (d.flags & ~kGRowFill) | ((rowfill && R == 1 && !dirs_lds) ? kGRowFill : 0);
   if (!dirs_lds) lds = lds_bytes_gg(d.rlength, d.glengthL, d.glengthR, R, false, std::max(WL, WR));
   // bridge candidates (+ direction planes) in global scratch
   c.gdirs = (scratch_bytes_gg(d.rlength, d.glengthL, d.glengthR, R, dirs_lds, std::max(WL, WR)) + 255) & ~(size_t)255;
@@ -1507,6 +1512,7 @@ static ClassOf classify_gdev(DevGenomeProblem& d, bool latency, size_t lds_dirs_
 
 static int classify(gmapdp_ctx* ctx, PlanCore& plan) {
   const size_t lds_dirs_max = gg_lds_dirs_max();  // read once per plan, not per genome-gap problem
+  const bool rowfill = gg_rowfill();
   const size_t nd = plan.dev.size(), ng = plan.gdev.size();
   const int T = plan_threads(nd + ng);
   // Latency mode (small batches: the GMAP drop-in's dispatcher batches): one launch class per (kind, R,
@@ -1524,7 +1530,7 @@ static int classify(gmapdp_ctx* ctx, PlanCore& plan) {
         c = classify_dev(plan.dev[s], latency);
         if (!c.err) class_work(c, plan.dev[s]);
       } else {
-        c = classify_gdev(plan.gdev[s - nd], latency, lds_dirs_max);
+        c = classify_gdev(plan.gdev[s - nd], latency, lds_dirs_max, rowfill);
         if (!c.err) class_work(c, plan.gdev[s - nd]);
       }
       if (c.err && first_err[t] == SIZE_MAX) first_err[t] = s;
@@ -2801,7 +2807,7 @@ int gmapdp_plan_launch_member_scratch(const gmapdp_plan* plan, int li, uint64_t*
       put(k, L.gdirs_offset, k == 0 ? (uint64_t)((nblocks * L.extra + 255) & ~(size_t)255) : 0);
     } else if (genome) {
       DevGenomeProblem d = in.gdev[in.gorder[L.first + k]];
-      put(k, (uint64_t)d.dirs_offset, classify_gdev(d, latency, lds_dirs_max).gdirs);
+      put(k, (uint64_t)d.dirs_offset, classify_gdev(d, latency, lds_dirs_max, gg_rowfill()).gdirs);
     } else {
       DevProblem d = in.dev[in.order[L.first + k]];
       const uint64_t o = (uint64_t)d.dirs_offset;  // (classify_dev resets its copy's)

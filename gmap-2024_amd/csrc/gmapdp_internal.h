@@ -66,6 +66,7 @@ constexpr int32_t kGSegRLeft = 0x2000;  // rev_gsequenceR via Genome_get_segment
 constexpr int32_t kGSegRRc = 0x4000;
 constexpr int32_t kGSimd = 0x8000;      // SIMD-build semantics (triangle fills, uxg_kernel)
 constexpr int32_t kGKnown = 0x10000;    // known splice sites: flags at known_offset (GMAPDP_KNOWN_SITES)
+constexpr int32_t kGRowFill = 0x20000;  // one-word bands take the row-held fill (set by the plan; GMAPDP_GG_ROWFILL=0 clears it)
 constexpr int kKnownReward = 20;        // KNOWN_SPLICESITE_REWARD (dynprog_genome.c:118)
 constexpr int32_t kUnset = (int32_t)0x80000000;  // out-parameter the reference leaves unwritten
 

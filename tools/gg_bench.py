@@ -16,6 +16,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gmap-2024_amd"))
 VARIANTS = {"gg_kernel": {}, "gg_kernel_lds_dirs": {"GMAPDP_GG_LDS_DIRS_MAX": str(48 * 1024)},
+            # every fill in the band-lane layout (fill_band) instead of the row-held one (fill_stretch)
+            "gg_kernel_bandfill": {"GMAPDP_GG_ROWFILL": "0"},
             # an earlier build of the library kept under gmap-2024_amd/lib_base (A/B of a kernel change)
             "lib_base": {"GMAPDP_LIB": os.path.join(ROOT, "gmap-2024_amd", "lib_base", "libgmapdp.so")}}
 
