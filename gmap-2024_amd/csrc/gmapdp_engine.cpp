@@ -89,6 +89,7 @@ hipError_t launch_cg(bool simd, int RB, int nproblems, size_t lds, hipStream_t s
                      const char* qseq, const char* qseq_uc, const int8_t* sctab, const uint8_t* constab,
                      gmapdp_cdna_result* results, gmapdp_pair* pairs);
 size_t lds_bytes_oi(int umax, bool wide);
+size_t scratch_bytes_oi_long();  // the long class's per-id tables, in front of the problem's scratch region
 size_t scratch_bytes_oi(int querylength, uint32_t genomiclength);
 size_t scratch_bytes_oi_fallback(int querylength, uint32_t genomiclength);
 size_t scratch_bytes_s2c(int querylength, int totalpositions, int ndiagonals);
@@ -112,10 +113,10 @@ hipError_t launch_oi(bool wide, int nproblems, size_t lds, hipStream_t stream, c
                      const uint32_t* blocks, const char* quc, unsigned char* scratch, gmapdp_oligo_result* results,
                      int32_t* npos, int32_t* map, uint32_t* table, int32_t* diags, uint64_t* pool,
                      unsigned long long* pool_counter, unsigned long long pool_cap, int32_t* nhits_out,
-                     bool modal);
+                     bool modal, bool longq);
 size_t scratch_bytes_oi_hits(int querylength, size_t hitcap);
 // Stage2_scan: one sub-batch's gather, table and scan kernels (`extra`: DevScanExtra records)
-hipError_t launch_s2scan(bool wide, bool modal, int nproblems, size_t lds, hipStream_t stream,
+hipError_t launch_s2scan(bool wide, bool modal, bool longq, int nproblems, size_t lds, hipStream_t stream,
                          const DevOligoProblem* probs, const void* extra, const uint32_t* blocks, const char* quc_all,
                          char* quc_priv, unsigned char* scratch, gmapdp_oligo_result* ores, int32_t* npos, int32_t* map,
                          uint32_t* table, int32_t* diags, uint64_t* pool, unsigned long long* pool_counter,
@@ -351,6 +352,8 @@ struct gmapdp_ctx {
   int plan_sides = kAux;     // side streams a plan's LPT spreads over (GMAPDP_CTX_TWO_SIDES: 2)
   hipEvent_t ev_block = nullptr;  // GMAPDP_CTX_BLOCKING_SYNC / _POLL_SYNC: batch completion waited on without spinning
   bool poll = false;              // GMAPDP_CTX_POLL_SYNC: ev_block is polled with sleeps in between
+  bool long_queries = false;      // GMAPDP_CTX_LONG_QUERIES: the seeding's long class (oligo_classify)
+  std::atomic<unsigned long long> long_calls{0};  // seeding problems classified long so far
   DevBuf probs, order, qseq, qseq_uc, results, pairs, gdirs;
   DevBuf din, dout;    // run_batch: all inputs / all outputs of one synchronous batch
   HostBuf hin, hout;   // their pinned host images
@@ -559,6 +562,7 @@ int gmapdp_create_ex(gmapdp_ctx** out, int device, int mode, int user_open, int 
   ctx->user_dynprog_p = user_dynprog_p;
   ctx->one_stream = (flags & GMAPDP_CTX_ONE_STREAM) != 0;
   ctx->plan_sides = (flags & GMAPDP_CTX_TWO_SIDES) ? 2 : gmapdp_ctx::kAux;
+  ctx->long_queries = (flags & GMAPDP_CTX_LONG_QUERIES) != 0;
   hipError_t e = hipSetDevice(device);
   int prio_least = 0, prio_greatest = 0;
   if (e == hipSuccess && (flags & (GMAPDP_CTX_PRIO_HIGH | GMAPDP_CTX_PRIO_LOW)))
@@ -2957,6 +2961,12 @@ void* gmapdp_stream(gmapdp_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr
 // Stage2_compute calls them for GMAP (stage2.c:6480-6495).  Synchronous batch path.
 // ---------------------------------------------------------------------------
 static const int kOligoMaxDistinct = 16384;
+// The long class (GMAPDP_CTX_LONG_QUERIES): more distinct 8-mers than the LDS classes hold, up to all 65 536.
+// Its per-id tables are global (oi_kernel.hip) and always 32-bit, so the class has one key, an odd one: it
+// sorts after every LDS class and gmapdp_stage2_plan_seeding_classes counts it with n32.
+static const int kOligoLongIds = 65536;
+static const int kOligoLongKey = 2 * kOligoLongIds + 1;
+static bool oligo_key_long(int key) { return (key >> 1) > kOligoMaxDistinct; }
 
 // 8-mer starts the tally visits (count_positions_fwd/rev_std, oligoindex_hr.c:19268-19281)
 static uint64_t oligo_window(const gmapdp_oligo_problem& p) {
@@ -3062,11 +3072,17 @@ static int oligo_classify(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problems,
       const uint64_t h = (lpl >> 4) + 1;
       if (3 * (h >> 1) + 1 >= ctx->genome_words) return bad(ctx, "stage-2 window past the genome");
     }
-    if (distinct[i] > kOligoMaxDistinct) return bad(ctx, "query with more than 16384 distinct 8-mers");
-    int umax = kBuckets[0];
-    for (int b : kBuckets)
-      if (distinct[i] <= b) { umax = b; break; }
-    C.key[i] = 2 * umax + (win >= 65536 ? 1 : 0);
+    if (distinct[i] > kOligoMaxDistinct && !ctx->long_queries)
+      return bad(ctx, "query with more than 16384 distinct 8-mers");
+    if (distinct[i] > kOligoMaxDistinct) {
+      C.key[i] = kOligoLongKey;
+      ctx->long_calls.fetch_add(1, std::memory_order_relaxed);
+    } else {
+      int umax = kBuckets[0];
+      for (int b : kBuckets)
+        if (distinct[i] <= b) { umax = b; break; }
+      C.key[i] = 2 * umax + (win >= 65536 ? 1 : 0);
+    }
     C.slots[i] = oligo_pool_slots(p);
     C.classes[C.key[i]].push_back(i);
   }
@@ -3181,13 +3197,15 @@ static void oligo_layout(gmapdp_oligo_plan* P, const std::vector<size_t>& slots,
   for (int k = 0; k < (int)P->ord.size(); k++) {
     DevOligoProblem& d = P->ord[k];
     const uint32_t w = d.chrend > d.chrstart ? d.chrend - d.chrstart : 0;
-    const size_t mb = align_up(hcap ? scratch_bytes_oi_hits(d.querylength, (*hcap)[d.index])
-                                    : scratch_bytes_oi(d.querylength, w), 256);
+    // (a long problem's per-id tables sit in front of its region: part of the chunk's bytes like the rest)
+    const size_t lt = oligo_key_long(P->keys[k]) ? scratch_bytes_oi_long() : 0;
+    const size_t mb = lt + align_up(hcap ? scratch_bytes_oi_hits(d.querylength, (*hcap)[d.index])
+                                         : scratch_bytes_oi(d.querylength, w), 256);
     const size_t fb = fallback ? align_up(scratch_bytes_oi_fallback(d.querylength, w), 256) : 0;
     if (k > first && (P->keys[k] != P->keys[first] || k - first >= kOligoChunkProblems ||
                       cb + mb + fb > (local ? kOligoSizingChunkBytes : kOligoChunkBytes)))
       close(k);
-    d.scratch_offset = (int64_t)cb;
+    d.scratch_offset = (int64_t)(cb + lt);
     d.fallback_offset = fallback ? (int64_t)(cb + mb) : -1;
     d.table_offset = (int64_t)ct;
     d.diag_offset = (int64_t)cd;
@@ -3298,7 +3316,8 @@ static hipError_t oligo_plan_relayout(gmapdp_ctx* ctx, gmapdp_oligo_plan* P, con
     std::vector<int> key(n), idx(n);
     for (int k = 0; k < n; k++) {
       const int i = P->ord[k].index;
-      key[k] = (P->keys[k] & 1) && nhits[i] >= 0 && nhits[i] < 65536 ? P->keys[k] - 1 : P->keys[k];
+      key[k] = (P->keys[k] & 1) && !oligo_key_long(P->keys[k]) && nhits[i] >= 0 && nhits[i] < 65536 ? P->keys[k] - 1
+                                                                                                     : P->keys[k];
       idx[k] = k;
     }
     std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return key[a] < key[b]; });
@@ -3362,12 +3381,15 @@ int gmapdp_oligo_plan_run(gmapdp_ctx* ctx, const gmapdp_oligo_plan* plan, const 
     if (hipMemsetAsync(plan->d_pool_counter, 0, sizeof(unsigned long long), s) != hipSuccess)
       return fail(ctx, GMAPDP_ELAUNCH, "oligo pool reset: %s", hipGetLastError());
     const int key = plan->umax[li];
+    // (the split kernels keep the per-id tables in LDS: a synchronous batch's long chunks take the one-pass
+    // kernels, over the same scratch layout)
+    const bool longq = oligo_key_long(key);
     const hipError_t e =
-        !plan->split
+        !plan->split || longq
             ? launch_oi(key & 1, plan->launches[li].second, lds_bytes_oi(key >> 1, key & 1), s,
                         plan->d_probs + plan->launches[li].first, ctx->d_genome, d_qseq_uc, plan->d_scratch,
                         d_results, d_npositions, d_mappings, d_positions, d_diagonals, plan->d_pool,
-                        plan->d_pool_counter, plan->pool_cap, plan->d_nhits, modal)
+                        plan->d_pool_counter, plan->pool_cap, plan->d_nhits, modal, longq)
             : launch_oi_split(plan->launches[li].second, key >> 1, s, plan->d_probs + plan->launches[li].first,
                               ctx->d_genome, d_qseq_uc, plan->d_scratch, d_results, d_npositions, d_mappings,
                               d_positions, d_diagonals, plan->d_pool, plan->d_pool_counter, plan->pool_cap, modal);
@@ -3522,7 +3544,8 @@ int gmapdp_scan_plan_create(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problem
     for (int i : kv.second) {
       const gmapdp_oligo_problem& p = problems[i];
       const uint32_t w = p.chrend > p.chrstart ? p.chrend - p.chrstart : 0;
-      const size_t mb = align_up(scratch_bytes_oi(p.querylength, w), 256);
+      const size_t lt = oligo_key_long(kv.first) ? scratch_bytes_oi_long() : 0;  // (see oligo_layout)
+      const size_t mb = lt + align_up(scratch_bytes_oi(p.querylength, w), 256);
       const size_t fb = align_up(scratch_bytes_oi_fallback(p.querylength, w), 256);
       const size_t tcap = oligo_table_cap(p), dcap = oligo_diag_cap(p);
       // (the event pool's share as the seeding plans estimate it; a problem with more events than the
@@ -3542,7 +3565,7 @@ int gmapdp_scan_plan_create(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problem
       d.index = L.count;     // its seeding record within the sub-batch
       d.table_offset = (int64_t)ct;
       d.diag_offset = (int64_t)cd;
-      d.scratch_offset = (int64_t)cs;
+      d.scratch_offset = (int64_t)(cs + lt);
       d.fallback_offset = (int64_t)(cs + mb);
       d.hit_cap = (uint32_t)std::min<size_t>((size_t)w + 2, 0xffffffffu);
       d.table_cap = (uint32_t)std::min<size_t>(tcap, 0xffffffffu);
@@ -3591,7 +3614,7 @@ int gmapdp_scan_plan_run(gmapdp_ctx* ctx, const gmapdp_scan_plan* plan, const ch
   for (const ScanLaunch& L : plan->launches) {
     // the sub-batches reuse one arena, in stream order
     const hipError_t e = launch_s2scan(
-        L.key & 1, plan->mode != 0, L.count, lds_bytes_oi(L.key >> 1, L.key & 1), s, plan->d_probs + L.first,
+        L.key & 1, plan->mode != 0, oligo_key_long(L.key), L.count, lds_bytes_oi(L.key >> 1, L.key & 1), s, plan->d_probs + L.first,
         plan->d_extra + 8 * (size_t)L.first, ctx->d_genome, d_qseq_uc, reinterpret_cast<char*>(A + L.quc),
         A + L.scratch, reinterpret_cast<gmapdp_oligo_result*>(A + L.ores), reinterpret_cast<int32_t*>(A + L.npos),
         reinterpret_cast<int32_t*>(A + L.map), reinterpret_cast<uint32_t*>(A + L.table),
@@ -4552,6 +4575,10 @@ int gmapdp_stage2_plan_seeding_classes(const gmapdp_stage2_plan* plan, int* n16,
   if (n16) *n16 = a;
   if (n32) *n32 = b;
   return GMAPDP_OK;
+}
+
+unsigned long long gmapdp_long_query_calls(const gmapdp_ctx* ctx) {
+  return ctx ? ctx->long_calls.load(std::memory_order_relaxed) : 0ull;
 }
 
 void gmapdp_stage2_plan_destroy(gmapdp_stage2_plan* plan) { delete plan; }

@@ -624,6 +624,28 @@ constexpr bool kOiStage = true;
 constexpr bool kOiStage = false;
 #endif
 
+// ---- the long class: queries with more than 16 384 distinct 8-mers (GMAPDP_CTX_LONG_QUERIES) ----
+// The per-id count and offset tables of such a query (up to 65 536 ids, 2 x 4 B each: 512 KB) cannot share a
+// CU's LDS, so they live in global memory, in a region that precedes the problem's scratch (the layouts put
+// kOiLongTableBytes in front of scratch_offset for a problem of this class); the bitmap and its ranks stay in
+// LDS.  The counters are always 32-bit.  Pass 1 counts with global atomics (both waves); the layout walk and
+// pass 2 run on wave 0 alone and use plain stores and L1-bypassing loads, ordered once per group of 64
+// elements by oi_long_sync: the walk is as sequential as in LDS, each group paying an L2 round trip.
+constexpr int kOiLongIds = 65536;
+constexpr size_t kOiLongTableBytes = 2 * sizeof(uint32_t) * (size_t)kOiLongIds;
+// a wave's earlier global stores are complete (vmcnt counts stores on gfx9) before its later loads issue
+__device__ __forceinline__ void oi_long_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_wave_barrier();
+}
+// a per-id table entry: LDS, or (long class) global memory read past the L1, which atomics do not update
+template <bool kLong, typename CT>
+__device__ __forceinline__ uint32_t oi_tab(const CT* p) {
+  if constexpr (kLong) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else return (uint32_t)*p;
+}
+
 #define OI_PASS_ARGS                                                                                          \
   const DevOligoProblem *__restrict__ probs, const uint32_t *__restrict__ blocks, const char *__restrict__ quc_all, \
       unsigned char *__restrict__ scratch, gmapdp_oligo_result *__restrict__ results,                             \
@@ -631,8 +653,10 @@ constexpr bool kOiStage = false;
       unsigned long long *__restrict__ pool_counter, unsigned long long pool_cap, int32_t *__restrict__ nhits_out
 // kModal: a cmet / atoi / ttoc context's instantiation, which reduces every genome word pair (P.reduce,
 // oi_reduce.h) before the strand handling; the STANDARD one carries none of it.
-template <typename CT, bool kModal>
+// kLong: the long class (CT uint32_t; cnt / offs in global memory, 16-bit ids in the hit list).
+template <typename CT, bool kModal, bool kLong = false>
 __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
+  static_assert(!kLong || sizeof(CT) == 4, "the long class counts in 32 bits");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int nh_wave[kOiWaves];  // each wave's pass-1 hits
   const int tid = threadIdx.x, lane = tid & 63;
@@ -640,8 +664,10 @@ __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
   const DevOligoProblem P = probs[blockIdx.x];
   uint32_t* bitmap = reinterpret_cast<uint32_t*>(smem);                  // 2048 words
   uint16_t* wrank = reinterpret_cast<uint16_t*>(smem + 4 * kOiWords);     // set bits before word w
-  CT* cnt = reinterpret_cast<CT*>(smem + 6 * kOiWords);                   // per id: count, then remaining | placed << 8
-  CT* offs = cnt + P.umax;                                                // per id: table offset
+  // per id: count, then remaining | placed << 8; per id: table offset (long class: before the scratch region)
+  CT* cnt = kLong ? reinterpret_cast<CT*>(scratch + P.scratch_offset - kOiLongTableBytes)
+                  : reinterpret_cast<CT*>(smem + 6 * kOiWords);
+  CT* offs = cnt + P.umax;
   const char* quc = quc_all + P.qoff;
   const int qlen = P.querylength;
   OI_MARK(0);
@@ -704,6 +730,7 @@ __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
     return;
   }
   for (int u = tid; u < U; u += 64 * kOiWaves) cnt[u] = 0;
+  if constexpr (kLong) __threadfence();  // the zeros reach L2 before the other wave's atomics
   __syncthreads();
 
   // ---- pass 1: counts of the window's query 8-mers ----
@@ -718,8 +745,9 @@ __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
   uint2* hitlist = reinterpret_cast<uint2*>(base_s + so.hits);
   uint32_t* hitlist32 = reinterpret_cast<uint32_t*>(base_s + so.hits);
   // hits as (window index << 14 | id) when the window has at most 2^18 starts (ids are below 2^14): half the
-  // bytes the list writes and pass 2 reads back
-  const bool compact = npos <= (1ull << 18);
+  // bytes the list writes and pass 2 reads back (long class: 16-bit ids, so << 16 and at most 2^16 starts)
+  constexpr int kIdShift = kLong ? 16 : 14;
+  const bool compact = npos <= (1ull << (32 - kIdShift));
   int nhits = 0;
   if (npos > 0) {
     // this wave's steps of 64 half-words: wave 0 the first half of the window's, wave 1 the rest
@@ -785,7 +813,7 @@ __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
         if ((uint32_t)o < P.hit_cap) {
           const uint32_t at = wave ? P.hit_cap - 1 - (uint32_t)o : (uint32_t)o;
           const uint32_t k = (uint32_t)(16 * h + j - left);
-          if (compact) hitlist32[at] = (k << 14) | (uint32_t)id;
+          if (compact) hitlist32[at] = (k << kIdShift) | (uint32_t)id;
           else hitlist[at] = make_uint2(k, (uint32_t)id);
         }
         o++;
@@ -807,12 +835,14 @@ __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
     }
   }
   if (lane == 0) nh_wave[wave] = nhits;
+  if constexpr (kLong) __threadfence();  // both waves' atomics and hit-list entries, for wave 0's plain loads
   __syncthreads();
   const int n0 = nh_wave[0], n1 = nh_wave[1];
   nhits = n0 + n1;
   if (nhits_out && tid == 0) nhits_out[P.index] = nhits;  // the hit list's length (a plan's sizing run)
   // Count_T wraps: each id's kept count, count & 255 (the bits above it: the layout's "placed" flag)
-  for (int u = tid; u < U; u += 64 * kOiWaves) cnt[u] = (CT)((uint32_t)cnt[u] & 255u);
+  for (int u = tid; u < U; u += 64 * kOiWaves) cnt[u] = (CT)(oi_tab<kLong>(&cnt[u]) & 255u);
+  if constexpr (kLong) __threadfence();
   __syncthreads();
   // The table slices follow QUERY order (wave 0; the total to both waves): the query positions in order, 64
   // at a time, each id's slice placed where the query first uses it, so that the consumers, which walk the
@@ -847,7 +877,7 @@ __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
         if (mm[r] >= 0) {
           bool in;
           id = oligo_id(bitmap, wrank, (uint32_t)mm[r], in);
-          cv = (uint32_t)cnt[id];  // every lane reads before the first lane of each id sets the flag
+          cv = oi_tab<kLong>(&cnt[id]);  // every lane reads before the first lane of each id sets the flag
         }
         const bool cand = id >= 0 && (cv >> 8) == 0u;
         uint64_t eq = ballot(cand);
@@ -864,14 +894,15 @@ __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
           cnt[id] = (CT)(cv | 0x100u);
         }
         tot += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        oi_wave_sync();
+        if constexpr (kLong) oi_long_sync();
+        else oi_wave_sync();
         int nh = -1;
         if (i < nq) {
           int mo = -1;
           if (id >= 0) {
             nh = (int)kept;
             npq[i] = nh;
-            if (nh > 0) mo = (int32_t)(uint32_t)offs[id];
+            if (nh > 0) mo = (int32_t)oi_tab<kLong>(&offs[id]);
           }
           mpq[i] = mo;
         }
@@ -921,7 +952,7 @@ __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
         at_n[r] = at;
         if (compact) {
           const uint32_t e = hitlist32[at];
-          hv_n[r] = make_uint2(e >> 14, e & 0x3FFFu);
+          hv_n[r] = make_uint2(e >> kIdShift, e & ((1u << kIdShift) - 1u));
         } else {
           hv_n[r] = hitlist[at];
         }
@@ -954,20 +985,21 @@ __device__ __forceinline__ void oi_pass(OI_PASS_ARGS) {
       if (id >= 0) {
         const int rank = lanes_below(eq, lane);
         const int same = __popcll(eq);
-        const uint32_t cv = (uint32_t)cnt[id];  // every lane reads before the first lane of each oligo writes
+        const uint32_t cv = oi_tab<kLong>(&cnt[id]);  // every lane reads before the first lane of each oligo writes
         const int r0 = (int)(cv & 255u);        // the remaining slots (above them: the placed flag)
-        const uint32_t slot = (uint32_t)offs[id] + (uint32_t)(r0 - rank - 1);
-        if (kOiStage && compact)
+        const uint32_t slot = oi_tab<kLong>(&offs[id]) + (uint32_t)(r0 - rank - 1);
+        if (kOiStage && !kLong && compact)
           slotarr[at] = r0 - rank > 0 ? slot : 0xFFFFFFFFu;
         else if (r0 - rank > 0)
           table[slot] = chrpos0 + (P.plusp ? k : (uint32_t)(npos - 1) - k);
         if (rank == 0) cnt[id] = (CT)(cv - (uint32_t)min(same, r0));
       }
+      if constexpr (kLong) oi_long_sync();  // the counts-down, before the next 64 hits read them
     }
   }
   __threadfence_block();
   __syncthreads();
-  if (kOiStage && compact) {  // every slot of [0, tot) is some hit's (a wrapped count keeps its first count & 255 hits)
+  if (kOiStage && !kLong && compact) {  // every slot of [0, tot) is some hit's (a wrapped count keeps its first count & 255 hits)
     uint32_t* stage = reinterpret_cast<uint32_t*>(smem);  // the bitmap and ranks (12 KB)
     constexpr uint32_t kStage = 6 * kOiWords / 4;
     for (uint32_t b0 = 0; b0 < tot; b0 += kStage) {
@@ -1169,6 +1201,13 @@ template <typename CT, bool kModal>
 __global__ __launch_bounds__(64 * kOiWaves) void oi_size_kernel(OI_PASS_ARGS) {
   oi_pass<CT, kModal>(probs, blocks, quc_all, scratch, results, npos_out, map_out, table_all, pool_counter, pool_cap,
               nhits_out);
+}
+// The long class's (one kernel for the plans' runs, their sizing runs and the synchronous batches, whose split
+// kernels' LDS cannot hold the class).
+template <bool kModal>
+__global__ __launch_bounds__(64 * kOiWaves) void oi_long_kernel(OI_PASS_ARGS) {
+  oi_pass<uint32_t, kModal, true>(probs, blocks, quc_all, scratch, results, npos_out, map_out, table_all, pool_counter,
+                                  pool_cap, nhits_out);
 }
 
 // ---- Oligoindex_get_mappings' diagonal state machine, one wave per problem, after oi_kernel ----
@@ -1773,7 +1812,9 @@ size_t lds_bytes_oib(int umax, int* tcap) {
   // the table image: 9 472 entries keeps r2 + image within a third of the CU's LDS for 2-kb reads (3
   // workgroups per CU) and holds a 214-kb window's ~8 300 hits.  GMAPDP_OI_LDS_TABLE (tests) caps it: 0 sends
   // every table and every non-empty candidate list to the global paths.
-  int t = (163840 - r2) / 4;
+  // (256 B stay free for the kernel's static LDS: the 16 384-id class, the only one whose image the CU's
+  // 160 KB bound rather than `lim`, asked for all of them and its launch was refused)
+  int t = (163840 - 256 - r2) / 4;
   int lim = 9472;
   if (const char* ev = std::getenv("GMAPDP_OI_LDS_TABLE")) lim = std::atoi(ev);
   if (t > lim) t = lim;
@@ -1818,7 +1859,11 @@ extern "C" int gmapdp_debug_oi_marks(unsigned long long* out) {
 }
 #endif
 
-size_t lds_bytes_oi(int umax, bool wide) { return 6 * (size_t)kOiWords + (wide ? 8 : 4) * (size_t)umax; }
+size_t lds_bytes_oi(int umax, bool wide) {
+  if (umax > 16384) return 6 * (size_t)kOiWords;  // the long class: the bitmap and its ranks alone
+  return 6 * (size_t)kOiWords + (wide ? 8 : 4) * (size_t)umax;
+}
+size_t scratch_bytes_oi_long() { return kOiLongTableBytes; }
 size_t scratch_bytes_oi(int querylength, uint32_t genomiclength) {
   return scratch_oi(querylength, genomiclength).total;
 }
@@ -1833,10 +1878,12 @@ hipError_t launch_oi(bool wide, int nproblems, size_t lds, hipStream_t stream, c
                      const uint32_t* blocks, const char* quc, unsigned char* scratch, gmapdp_oligo_result* results,
                      int32_t* npos, int32_t* map, uint32_t* table, int32_t* diags, uint64_t* pool,
                      unsigned long long* pool_counter, unsigned long long pool_cap, int32_t* nhits_out,
-                     bool modal) {
+                     bool modal, bool longq) {
   const bool sizing = nhits_out != nullptr;  // a stage-2 plan's sizing run: the same code, its own names
   // (the map kernels read the table, never the genome: one instantiation serves every mode)
-  void* fn = modal ? (sizing ? (wide ? reinterpret_cast<void*>(&oi_size_kernel<uint32_t, true>)
+  void* fn = longq ? (modal ? reinterpret_cast<void*>(&oi_long_kernel<true>)
+                            : reinterpret_cast<void*>(&oi_long_kernel<false>))
+             : modal ? (sizing ? (wide ? reinterpret_cast<void*>(&oi_size_kernel<uint32_t, true>)
                                      : reinterpret_cast<void*>(&oi_size_kernel<uint16_t, true>))
                              : (wide ? reinterpret_cast<void*>(&oi_kernel<uint32_t, true>)
                                      : reinterpret_cast<void*>(&oi_kernel<uint16_t, true>)))

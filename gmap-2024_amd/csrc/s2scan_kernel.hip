@@ -55,6 +55,12 @@ __global__ __launch_bounds__(64 * kOiWaves) void s2scan_table_kernel(OI_PASS_ARG
                       nhits_out);
 }
 
+template <bool kModal>  // the long class (oi_long_kernel's pass)
+__global__ __launch_bounds__(64 * kOiWaves) void s2scan_table_long_kernel(OI_PASS_ARGS) {
+  oi_pass<uint32_t, kModal, true>(probs, blocks, quc_all, scratch, results, npos_out, map_out, table_all, pool_counter,
+                                  pool_cap, nhits_out);
+}
+
 // query positions the LDS bitmap holds (512 B of the 4-KB histogram); longer queries: the global difference array
 constexpr int kScanBitmapBits = 4096;
 static_assert(kScanBitmapBits / 32 <= kOiHist, "the coverage bitmap aliases the radix histogram");
@@ -173,7 +179,7 @@ __global__ __launch_bounds__(64) void s2scan_kernel(
 }
 
 // One sub-batch: gather, table, scan, in stream order.  `extra` as raw bytes (DevScanExtra is this file's).
-hipError_t launch_s2scan(bool wide, bool modal, int nproblems, size_t lds, hipStream_t stream,
+hipError_t launch_s2scan(bool wide, bool modal, bool longq, int nproblems, size_t lds, hipStream_t stream,
                          const DevOligoProblem* probs, const void* extra, const uint32_t* blocks, const char* quc_all,
                          char* quc_priv, unsigned char* scratch, gmapdp_oligo_result* ores, int32_t* npos, int32_t* map,
                          uint32_t* table, int32_t* diags, uint64_t* pool, unsigned long long* pool_counter,
@@ -183,7 +189,9 @@ hipError_t launch_s2scan(bool wide, bool modal, int nproblems, size_t lds, hipSt
                      quc_priv, pool_counter);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  void* fn = modal ? (wide ? reinterpret_cast<void*>(&s2scan_table_kernel<uint32_t, true>)
+  void* fn = longq ? (modal ? reinterpret_cast<void*>(&s2scan_table_long_kernel<true>)
+                            : reinterpret_cast<void*>(&s2scan_table_long_kernel<false>))
+             : modal ? (wide ? reinterpret_cast<void*>(&s2scan_table_kernel<uint32_t, true>)
                            : reinterpret_cast<void*>(&s2scan_table_kernel<uint16_t, true>))
                    : (wide ? reinterpret_cast<void*>(&s2scan_table_kernel<uint32_t, false>)
                            : reinterpret_cast<void*>(&s2scan_table_kernel<uint16_t, false>));

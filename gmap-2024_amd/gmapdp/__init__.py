@@ -21,6 +21,7 @@ WATSON, JUMP_LATE, WIDEBAND = 0x1, 0x2, 0x4
 DEVICE = "device"  # splice / candidate probabilities evaluated by the engine's device MaxEnt (a NULL arena)
 CTX_ONE_STREAM, CTX_PRIO_HIGH, CTX_PRIO_LOW, CTX_BLOCKING_SYNC, CTX_POLL_SYNC = 0x1, 0x2, 0x4, 0x8, 0x10  # create_ex flags
 CTX_TWO_SIDES = 0x20
+CTX_LONG_QUERIES = 0x40  # stage 2 takes queries with more than 16384 distinct 8-mers (the long seeding class)
 SIMD = 0x40  # GMAPDP_SIMD: the reference's SIMD builds' semantics (every problem family)
 HALFP, FINALP = 0x8, 0x10
 KNOWN_SITES = 0x80  # GMAPDP_KNOWN_SITES: known splice sites of a genome gap (gmap -s)
@@ -290,6 +291,7 @@ def load_library(path=LIB_PATH):
                                                C.c_size_t, C.c_void_p, C.c_size_t, P(C.c_size_t), P(C.c_size_t)]),
         "gmapdp_stage2_plan_seeding_classes": (C.c_int, [C.c_void_p, P(C.c_int), P(C.c_int)]),
         "gmapdp_stage2_plan_seeding_results": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "gmapdp_long_query_calls": (C.c_ulonglong, [C.c_void_p]),
         "gmapdp_stage2_plan_destroy": (None, [C.c_void_p]),
         "gmapdp_genome_prob_entries": (C.c_size_t, [C.c_void_p, C.c_int]),
         "gmapdp_genome_splice_sites": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -793,6 +795,64 @@ class Engine:
             out.append(((int(r["totalpositions"]), int(r["maxnconsecutive"]), int(r["oned_matrix_p"]), nd),
                         np_, plist, dg))
         return out
+
+    def _decode_oligo(self, probs, results, npos, maps, positions, diags, relative):
+        """The oracle's format from the raw arrays (relative: mappings index the call's own table)."""
+        out = []
+        for i, r in enumerate(results):
+            o, n = int(probs[i]["qoff"]), int(probs[i]["querylength"])
+            t0 = int(r["table_offset"]) if relative else 0
+            np_ = npos[o:o + n]
+            mp_ = maps[o:o + n]
+            hit = np.nonzero(np_ > 0)[0]
+            plist = np.concatenate([positions[t0 + int(mp_[q]):t0 + int(mp_[q]) + int(np_[q])] for q in hit]
+                                   or [np.zeros(0, dtype=np.uint32)]).tolist()
+            d0, nd = int(r["diag_offset"]), int(r["ndiagonals"])
+            dg = [tuple(int(x) for x in diags[4 * (d0 + k):4 * (d0 + k) + 4]) for k in range(nd)]
+            out.append(((int(r["totalpositions"]), int(r["maxnconsecutive"]), int(r["oned_matrix_p"]), nd),
+                        np_.tolist(), plist, dg))
+        return out
+
+    def oligo_plan_batch(self, calls):
+        """oligo_mappings_batch's results through the device-resident seeding plan (gmapdp_oligo_plan_create /
+        _run: the one-pass kernels), the arenas copied back afterwards."""
+        lib, hip = self.lib, _hip()
+        probs, qucbuf = self.build_oligo_batch(list(calls))
+        n = len(probs)
+        plan = C.c_void_p()
+        self._check(lib.gmapdp_oligo_plan_create(self.h, probs.ctypes.data, n, qucbuf, len(qucbuf), C.byref(plan)),
+                    "gmapdp_oligo_plan_create")
+        bufs = []
+        try:
+            pc = max(lib.gmapdp_oligo_plan_positions_capacity(plan), 1)
+            dc = max(lib.gmapdp_oligo_plan_diagonal_capacity(plan), 1)
+            arrs = [np.zeros(n, dtype=OLIGO_RESULT_DTYPE), np.zeros(len(qucbuf), dtype=np.int32),
+                    np.zeros(len(qucbuf), dtype=np.int32), np.zeros(pc, dtype=np.uint32),
+                    np.zeros(4 * dc, dtype=np.int32)]
+            dev = []
+            for src in [np.frombuffer(qucbuf, dtype=np.uint8)] + arrs:
+                ptr = C.c_void_p()
+                if hip.hipMalloc(C.byref(ptr), max(src.nbytes, 16)) != 0:
+                    raise GmapdpError("hipMalloc(%d) failed" % src.nbytes)
+                bufs.append(ptr)
+                if hip.hipMemcpy(ptr, src.ctypes.data, src.nbytes, 1) != 0:  # hipMemcpyHostToDevice
+                    raise GmapdpError("hipMemcpy failed")
+                dev.append(ptr)
+            self._check(lib.gmapdp_oligo_plan_run(self.h, plan, *dev, None), "gmapdp_oligo_plan_run")
+            if hip.hipDeviceSynchronize() != 0:
+                raise GmapdpError("hipDeviceSynchronize failed")
+            for a, d in zip(arrs, dev[1:]):
+                if hip.hipMemcpy(a.ctypes.data, d, a.nbytes, 2) != 0:  # hipMemcpyDeviceToHost
+                    raise GmapdpError("hipMemcpy failed")
+        finally:
+            for b in bufs:
+                hip.hipFree(b)
+            lib.gmapdp_oligo_plan_destroy(plan)
+        return self._decode_oligo(probs, *arrs, relative=True)
+
+    def long_query_calls(self):
+        """Seeding problems this context has put into the long class so far (CTX_LONG_QUERIES)."""
+        return int(self.lib.gmapdp_long_query_calls(self.h))
 
     # -- batched Stage2_scan (seeding with the major index + Diag_update_coverage) ------------------
     @staticmethod

@@ -128,6 +128,9 @@ static const char *const shim_stat_name[ST_N] = {"Dynprog_single_gap", "Dynprog_
                                                  "Dynprog_end3_known"};
 static unsigned long shim_stats[ST_N];
 static unsigned long shim_cross_species;  /* Stage2_compute calls sent with GMAPDP_S2_CANONICAL_MIDDLE */
+/* Oligoindex_get_mappings and Stage2_compute calls whose query (more than 16384 distinct 8-mers) seeded in the
+   engine's long class (the contexts are created with GMAPDP_CTX_LONG_QUERIES) */
+static unsigned long shim_long[2];
 
 static unsigned long shim_batches, shim_batched;
 static FILE *shim_trace = NULL;  /* GMAPDP_SHIM_TRACE: per-batch record (diagnostics) */
@@ -147,6 +150,8 @@ shim_print_stats (void) {
   fprintf(stderr, "gmapdp shim calls:");
   for (i = 0; i < ST_N; i++) fprintf(stderr, " %s=%lu", shim_stat_name[i], __atomic_load_n(&shim_stats[i], __ATOMIC_RELAXED));
   fprintf(stderr, " Stage2_compute_cross_species=%lu", __atomic_load_n(&shim_cross_species, __ATOMIC_RELAXED));
+  fprintf(stderr, " Oligoindex_long=%lu Stage2_compute_long=%lu", __atomic_load_n(&shim_long[0], __ATOMIC_RELAXED),
+          __atomic_load_n(&shim_long[1], __ATOMIC_RELAXED));
   fprintf(stderr, " batches=%lu mean_batch=%.2f dp_s=%.3f cdna_s=%.3f stage2_s=%.3f chain_s=%.3f\n", shim_batches,
           shim_batches ? (double) shim_batched / (double) shim_batches : 0.0, shim_secs[0], shim_secs[1], shim_secs[2],
           shim_secs[3]);
@@ -516,7 +521,7 @@ shim_context (Genome_T genome) {
     const char *ms = getenv("GMAPDP_SHIM_MULTI_STREAM");
     const int one = (ms != NULL && ms[0] == '1' && shim_qi == 0) ? 0 : GMAPDP_CTX_ONE_STREAM;
     shim_check(gmapdp_create_ex(&shim_ctx, shim_device(), shim_mode, shim_user_open, shim_user_extend,
-                                shim_user_dynprog_p, one | wait |
+                                shim_user_dynprog_p, one | wait | GMAPDP_CTX_LONG_QUERIES |
                                     (shim_qi != 1 ? GMAPDP_CTX_PRIO_HIGH : GMAPDP_CTX_PRIO_LOW)),
                "gmapdp_create_ex");
   }
@@ -1349,8 +1354,12 @@ shim_run (shim_req *batch) {
     GROW(D.pos, D.poscap, pc + 1);
     GROW(D.dg, D.dgcap, 4 * dc + 4);
     GROW(D.ores, D.orescap, no + 1);
-    shim_check(gmapdp_oligo_mappings_batch(shim_ctx, D.o, (int) no, D.quc, qb, D.ores, D.np, D.mp, D.pos, pc, D.dg,
-                                           dc), "gmapdp_oligo_mappings_batch");
+    {
+      const unsigned long long l0 = gmapdp_long_query_calls(shim_ctx);
+      shim_check(gmapdp_oligo_mappings_batch(shim_ctx, D.o, (int) no, D.quc, qb, D.ores, D.np, D.mp, D.pos, pc, D.dg,
+                                             dc), "gmapdp_oligo_mappings_batch");
+      __atomic_fetch_add(&shim_long[0], (unsigned long) (gmapdp_long_query_calls(shim_ctx) - l0), __ATOMIC_RELAXED);
+    }
     for (i = 0; i < no; i++) {
       size_t q, ql;
       r = D.ro[i];
@@ -1390,9 +1399,12 @@ shim_run (shim_req *batch) {
     GROW(D.s2res, D.s2rescap, n2 + 1);
     GROW(D.paths, D.pathcap, 4 * n2 + 16);
     GROW(D.ppairs, D.ppaircap, 3 * qb + 64);
-    for (;;) {
+    for (k = 0;; k++) {
+      const unsigned long long l0 = gmapdp_long_query_calls(shim_ctx);
       rc = gmapdp_stage2_batch(shim_ctx, D.s2, (int) n2, D.q, D.quc, qb, D.s2res, D.paths, D.pathcap, D.ppairs,
                                D.ppaircap, &pneed, &qneed);
+      if (k == 0)  /* (a repeat with larger arrays classifies the same calls again) */
+        __atomic_fetch_add(&shim_long[1], (unsigned long) (gmapdp_long_query_calls(shim_ctx) - l0), __ATOMIC_RELAXED);
       if (rc != GMAPDP_ESPACE) break;
       GROW(D.paths, D.pathcap, pneed + 16);
       GROW(D.ppairs, D.ppaircap, qneed + 64);

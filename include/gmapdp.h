@@ -550,7 +550,10 @@ void gmapdp_microexon_plan_destroy (gmapdp_microexon_plan *plan);
  * at chroffset..chrhigh on the plus (plusp) or minus strand.  minor selects
  * Oligoindex_array_new_minor's index (diag_lookback 60, suffnconsecutive 10) instead of the major
  * one (120, 20).  Domain: querylength > 8 (Oligoindex_set_inquery leaves stale state below that)
- * and at most 16384 distinct query 8-mers.
+ * and at most 16384 distinct query 8-mers (a random sequence reaches that at about 18.9 kb).  A context
+ * created with GMAPDP_CTX_LONG_QUERIES takes any query: one with more than 16384 distinct 8-mers (up to
+ * all 65536) seeds in the "long" launch class, whose per-8-mer tables live in global memory, with the same
+ * results; every stage-2 entry point accepts it, and a batch may mix short and long problems.
  * The context's mode (gmapdp_create) is the tally's: STANDARD, or a stranded cmet / atoi / ttoc mode
  * (Mode_T 1, 3, 5), in which the window's genome words are reduced before the 8-mers are taken
  * (count / store_positions_{fwd,rev}_std, oligoindex_hr.c:19293 / :30795; the query is not reduced).
@@ -775,8 +778,12 @@ int gmapdp_stage2_plan_fetch (gmapdp_ctx *ctx, const gmapdp_stage2_plan *plan, c
 int gmapdp_stage2_plan_seeding_results (gmapdp_ctx *ctx, const gmapdp_stage2_plan *plan, void *stream,
                                         gmapdp_oligo_result *out);
 /* How many of the plan's calls seed with 16-bit and with 32-bit counters (after the plan's sizing run
- * moved every call with fewer than 2^16 hits to the 16-bit class). */
+ * moved every call with fewer than 2^16 hits to the 16-bit class).  Calls of the long class
+ * (GMAPDP_CTX_LONG_QUERIES), whose counters are always 32-bit, are counted with n32. */
 int gmapdp_stage2_plan_seeding_classes (const gmapdp_stage2_plan *plan, int *n16, int *n32);
+/* Seeding problems the context has put into the long class so far, over all its stage-2 entry points
+ * (0 for ever without GMAPDP_CTX_LONG_QUERIES). */
+unsigned long long gmapdp_long_query_calls (const gmapdp_ctx *ctx);
 /* The compact stream of a finished chaining run's path pairs (gmapdp_plan_compact_pairs' format, 21-B RAW
  * ops: gmapdp_path_pair records with a jump or a negative position): one list per record of the plan's path
  * pool (*path_cap of them; records past the pool's count are empty lists).  d_offsets: path_cap + 1 uint64
@@ -821,6 +828,10 @@ void gmapdp_destroy (gmapdp_ctx *ctx);
  * work of its own, e.g. Stage2_compute on its own stream beside the plan (bench.py), so that no stream
  * receives two of the plan's lists. */
 #define GMAPDP_CTX_TWO_SIDES 0x20
+/* Stage 2 takes queries with more than 16384 distinct 8-mers (gmapdp_oligo_problem's domain text); without
+ * the flag every stage-2 entry point refuses them with GMAPDP_EINVAL.  Queries within the bound seed exactly
+ * as without the flag. */
+#define GMAPDP_CTX_LONG_QUERIES 0x40
 int gmapdp_create_ex (gmapdp_ctx **ctx, int device, int mode, int user_open, int user_extend, int user_dynprog_p,
                       int flags);
 /* Use `owner`'s HBM-resident genome in `ctx` (no copy; same device).  `owner` must outlive every
