@@ -104,7 +104,7 @@ hipError_t launch_s2c(int nproblems, hipStream_t stream, const DevStage2Problem*
                       unsigned char* scratch, unsigned long long* counters, unsigned long long scratch_cap,
                       gmapdp_stage2_result* results, gmapdp_path* paths, unsigned long long path_cap,
                       gmapdp_path_pair* pairs, unsigned long long pair_cap, bool modal, int phases = 7,
-                      const double* canon_metab = nullptr);
+                      const double* canon_metab = nullptr, int kind = 0);
 int s2_canon_counters(unsigned long long* out8);
 hipError_t launch_canon_links(long long n, hipStream_t s, const uint32_t* blocks, uint64_t nwords, const double* T,
                               const gmapdp_coord_t* prevpos, const gmapdp_coord_t* currpos, int plusp,
@@ -3715,6 +3715,12 @@ static int s2_copy_out(gmapdp_ctx* ctx, hipStream_t s, const gmapdp_path* d_path
   return e == hipSuccess ? GMAPDP_OK : fail(ctx, GMAPDP_ELAUNCH, errfmt, e);
 }
 
+static int s2_batch_core(gmapdp_ctx* ctx, int n, std::vector<gmapdp_oligo_problem>& op,
+                         std::vector<DevStage2Problem>& dp, size_t qsum, const double* canon_metab, int kind,
+                         const char* qseq, const char* qseq_uc, size_t qbytes, gmapdp_stage2_result* results,
+                         gmapdp_path* paths, size_t path_cap, gmapdp_path_pair* pairs, size_t pair_cap,
+                         size_t* paths_needed, size_t* pairs_needed);
+
 extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem* problems, int n, const char* qseq,
                                    const char* qseq_uc, size_t qbytes, gmapdp_stage2_result* results,
                                    gmapdp_path* paths, size_t path_cap, gmapdp_path_pair* pairs, size_t pair_cap,
@@ -3731,8 +3737,19 @@ extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem*
   size_t qsum = 0;
   int rc = s2_problems(ctx, problems, n, &canon_metab, op, dp, &qsum);
   if (rc) return rc;
+  return s2_batch_core(ctx, n, op, dp, qsum, canon_metab, /*kind*/ 0, qseq, qseq_uc, qbytes, results, paths, path_cap,
+                       pairs, pair_cap, paths_needed, pairs_needed);
+}
+
+// The body of gmapdp_stage2_batch and gmapdp_stage2x_batch: the seeding of `op`, then the chaining of `dp` (kind:
+// the batch's DevStage2Problem.kind, which picks the sweep and the path kernels).
+static int s2_batch_core(gmapdp_ctx* ctx, int n, std::vector<gmapdp_oligo_problem>& op,
+                         std::vector<DevStage2Problem>& dp, size_t qsum, const double* canon_metab, int kind,
+                         const char* qseq, const char* qseq_uc, size_t qbytes, gmapdp_stage2_result* results,
+                         gmapdp_path* paths, size_t path_cap, gmapdp_path_pair* pairs, size_t pair_cap,
+                         size_t* paths_needed, size_t* pairs_needed) {
   std::unique_ptr<gmapdp_oligo_plan> plan;  // (views of the context's buffers: nothing to free)
-  rc = oligo_plan_build(ctx, op.data(), n, qseq_uc, qbytes, plan, true);
+  int rc = oligo_plan_build(ctx, op.data(), n, qseq_uc, qbytes, plan, true);
   if (rc) return rc;
   const size_t toff = plan->table_cap, doff = plan->diag_cap;
   hipStream_t s = ctx->stream;
@@ -3767,7 +3784,7 @@ extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem*
   size_t scratch = 0;
   for (int i = 0; i < n; i++) {
     dp[i].scratch_offset = (int64_t)scratch;
-    scratch += scratch_bytes_s2c(problems[i].querylength, ores[i].totalpositions, ores[i].ndiagonals);
+    scratch += scratch_bytes_s2c(dp[i].querylength, ores[i].totalpositions, ores[i].ndiagonals);
   }
   e = hipMemcpyAsync(ctx->s2probs.p, dp.data(), sizeof(DevStage2Problem) * n, hipMemcpyHostToDevice, s);
   if (e != hipSuccess) return fail(ctx, GMAPDP_ELAUNCH, "stage-2 descriptors: %s", e);
@@ -3784,7 +3801,7 @@ extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem*
                      (const int32_t*)ctx->odiag.p, (unsigned char*)ctx->s2scratch.p,
                      (unsigned long long*)ctx->s2counters.p, (unsigned long long)scratch,
                      (gmapdp_stage2_result*)ctx->s2results.p, (gmapdp_path*)ctx->s2paths.p, pcap,
-                     (gmapdp_path_pair*)ctx->s2pairs.p, qcap, ctx->mode != 0, 7, canon_metab);
+                     (gmapdp_path_pair*)ctx->s2pairs.p, qcap, ctx->mode != 0, 7, canon_metab, kind);
     unsigned long long cnt[4] = {0, 0, 0, 0};
     if (e == hipSuccess)
       e = hipMemcpyAsync(results, ctx->s2results.p, sizeof(gmapdp_stage2_result) * n, hipMemcpyDeviceToHost, s);
@@ -3804,6 +3821,43 @@ extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem*
     pcap = std::max<size_t>(2 * pcap, (size_t)cnt[1] + 16);
     qcap = std::max<size_t>(2 * qcap, (size_t)cnt[2] + 64);
   }
+}
+
+// Stage2_compute_one / Stage2_compute_ends (stage2.c:6754 / 7087) as stage 3 calls them: the seeding with the
+// minor oligoindex, then the chaining kernels' variants for the batch's kind (launch_s2c).
+extern "C" int gmapdp_stage2x_batch(gmapdp_ctx* ctx, const gmapdp_stage2x_problem* problems, int n, const char* qseq,
+                                    const char* qseq_uc, size_t qbytes, gmapdp_stage2_result* results,
+                                    gmapdp_path* paths, size_t path_cap, gmapdp_path_pair* pairs, size_t pair_cap,
+                                    size_t* paths_needed, size_t* pairs_needed) {
+  if (!ctx || n < 0 || (n > 0 && (!problems || !results || !qseq || !qseq_uc))) return GMAPDP_EINVAL;
+  if (paths_needed) *paths_needed = 0;
+  if (pairs_needed) *pairs_needed = 0;
+  if (!ctx->d_genome) {
+    ctx->err = "stage 2x: the context has no genome (gmapdp_set_genome)";
+    return GMAPDP_ENOGENOME;
+  }
+  if (n == 0) return GMAPDP_OK;
+  (void)hipSetDevice(ctx->device);
+  std::vector<gmapdp_oligo_problem> op(n);
+  std::vector<DevStage2Problem> dp(n);
+  size_t qsum = 0;
+  const int kind = problems[0].kind;
+  for (int i = 0; i < n; i++) {
+    const gmapdp_stage2x_problem& p = problems[i];
+    if (p.kind != GMAPDP_S2X_ONE && p.kind != GMAPDP_S2X_ENDS)
+      return bad(ctx, "stage 2x: kind is neither GMAPDP_S2X_ONE nor GMAPDP_S2X_ENDS");
+    if (p.kind != kind) return bad(ctx, "stage 2x: one batch takes one kind (GMAPDP_S2X_ONE and _ENDS are mixed)");
+    if (p.flags != 0) return bad(ctx, "stage 2x: flags must be 0 (no cross-species scoring for these calls)");
+    if (p.maxintronlen < 0) return bad(ctx, "stage 2x: negative maxintronlen");
+    // (minor 1: both calls take oligoindices_minor, stage3.c:11392 / 15853)
+    op[i] = gmapdp_oligo_problem{p.qoff, p.querylength, p.chrstart, p.chrend, p.chroffset, p.chrhigh,
+                                 p.plusp ? 1 : 0, 1};
+    dp[i] = DevStage2Problem{p.qoff, p.querylength, p.chrstart, p.chrend, p.chroffset, p.chrhigh, p.plusp ? 1 : 0,
+                             p.splicingp ? 1 : 0, (uint32_t)p.maxintronlen, i, 0, p.kind, p.query_offset};
+    qsum += (size_t)std::max(p.querylength, 0);
+  }
+  return s2_batch_core(ctx, n, op, dp, qsum, nullptr, kind, qseq, qseq_uc, qbytes, results, paths, path_cap, pairs,
+                       pair_cap, paths_needed, pairs_needed);
 }
 
 // ---------------------------------------------------------------------------

@@ -287,9 +287,21 @@ constexpr int kS2FormScalar = 0, kS2FormChunk = 1, kS2FormEval1 = 2, kS2FormFast
 __device__ unsigned long long g_s2_canon[8];
 // kCanon: the cross-species variant of the sweep (GMAPDP_S2_CANONICAL_MIDDLE): range 2 takes
 // NON_CANONICAL_PENALTY_MIDDLE off every link that canonical_link (canon_device.h) declines
-template <bool kC>
+// kLocal / kMiddle / kSkip: align_compute_lookback's localp, middlep and skip_repetitive_p.  Stage2_compute
+// passes true / true / true; Stage2_compute_one true / true / false; Stage2_compute_ends false / false / false
+// (DevStage2Problem.kind, one per launch).  Where the sweep depends on them:
+//   kLocal   a hit without a predecessor scores indexsize; else it keeps the search's 0 (stage2.c:1445-1451,
+//            :1551-1556, :1993-1999).  The shortcuts below never involve such a hit's score: the run on the last
+//            entry's diagonal links every member to a predecessor, and the one-wave windows (s2_dloop_fast /
+//            _multi) only read hits that are active, i.e. scored above 0 under either setting.
+//   kMiddle  else a position none of whose hits scored above 0 restarts every hit (:3955-3980): score and consec
+//            indexsize, no link, tracei -1 -- a value range 0 compares like any other (last_tr starts at -1).
+//   kSkip    the MAX_NACTIVE / MAX_SKIPPED branch (:3862-3887); without it every position goes through s2_one,
+//            the <= 64-hit form or s2_mult by its hit count alone.
+template <bool kC, bool kLocal = true, bool kMiddle = true, bool kSkip = true>
 struct S2WT {
   static constexpr bool kCanon = kC;
+  static constexpr bool kLocalp = kLocal, kMiddlep = kMiddle, kSkipRepetitive = kSkip;
   S2Hit* hits;
   const uint32_t* maps;  // chrpos per hit
   int* sc;               // score per hit (fwd_scores)
@@ -941,9 +953,9 @@ __device__ __forceinline__ S2Best s2_one(SW& W, int q, uint32_t position, int np
     S2_SUB(4);
   }
   s2_uniform(b);
-  if (b.pp < 0) {  // localp
+  if (b.pp < 0) {  // localp: indexsize; else the search's score, 0 (stage2.c:1445-1451)
     b.tracei = ++W.tracectr;
-    b.score = kS2K;
+    if constexpr (SW::kLocalp) b.score = kS2K;
   }
   return b;
 }
@@ -965,7 +977,8 @@ __device__ __forceinline__ void s2_mult(SW& W, int q, int offq, int low, int hig
   if (np == 0) {
     for (int i = W.lane; i < nhits; i += 64) {
       W.hits[offq + low + i] = S2Hit{kS2K, (int)W.maps[offq + low + i], W.tracectr + 1 + i, -1};
-      W.sc[offq + low + i] = kS2K;
+      if constexpr (SW::kLocalp) W.sc[offq + low + i] = kS2K;
+      else W.sc[offq + low + i] = 0;  // (:1555; its fwd_tracei stays unset: the restart below gives it -1)
     }
     W.tracectr += nhits;
     wave_sync();
@@ -1018,7 +1031,7 @@ __device__ __forceinline__ void s2_mult(SW& W, int q, int offq, int low, int hig
     }
     if (b.pp < 0) {
       b.tracei = ++W.tracectr;
-      b.score = kS2K;
+      if constexpr (SW::kLocalp) b.score = kS2K;
     }
     s2_store_link(W, offq, low + i, b);
   }
@@ -1173,17 +1186,19 @@ __device__ __forceinline__ void s2_sweep(SW& W, const int32_t* npq, int nq, cons
     const int n = __builtin_amdgcn_readlane(m_n, j);
     const int offq = __builtin_amdgcn_readlane(m_off, j);
     int low = __builtin_amdgcn_readlane(m_low, j), high = __builtin_amdgcn_readlane(m_high, j);
-    if (high - low >= kS2MaxNactive && nskipped <= kS2MaxSkipped) {
-      if (lane == 0) W.actn[q] = 0;
-      nskipped++;
-      if (high - low < min_hits) {
-        min_hits = high - low;
-        specific_q = q;
-        specific_low = low;
-        specific_high = high;
+    if constexpr (SW::kSkipRepetitive) {
+      if (high - low >= kS2MaxNactive && nskipped <= kS2MaxSkipped) {
+        if (lane == 0) W.actn[q] = 0;
+        nskipped++;
+        if (high - low < min_hits) {
+          min_hits = high - low;
+          specific_q = q;
+          specific_low = low;
+          specific_high = high;
+        }
+        q++;
+        continue;
       }
-      q++;
-      continue;
     }
     int next_q, qoff = offq;
     if (nskipped > kS2MaxSkipped) {
@@ -1204,6 +1219,11 @@ __device__ __forceinline__ void s2_sweep(SW& W, const int32_t* npq, int nq, cons
       S2Best b = s2_one(W, q, position, np, last);
       int best_score = b.score > 0 ? b.score : 0;
       const bool have_best = b.score > 0;
+      if constexpr (!SW::kMiddlep) {
+        // a new start (stage2.c:3955-3980; best_fwd_hit stays -1: no grand lookback, no new grand best).  It
+        // takes every hit of the position; these calls' bounds (Diag_max_bounds) leave none outside [low, high)
+        if (!have_best) b = {kS2K, b.root, -1, -1, kS2K, -1};
+      }
       nskipped = 0;
       min_hits = 1000000;
       specific_q = -1;
@@ -1247,7 +1267,7 @@ __device__ __forceinline__ void s2_sweep(SW& W, const int32_t* npq, int nq, cons
       const uint32_t cm = lane < nh ? W.maps[qoff + low + lane] : 0u;
       S2Best mb = {0, 0, -1, -1, 0, 0};
       if (np == 0) {
-        if (lane < nh) mb = {kS2K, (int)cm, -1, -1, kS2K, W.tracectr + 1 + lane};
+        if (lane < nh) mb = {kS2K, (int)cm, -1, -1, SW::kLocalp ? kS2K : 0, W.tracectr + 1 + lane};
         W.tracectr += nh;
       } else {
         const int adq = q - last.q;
@@ -1387,7 +1407,7 @@ __device__ __forceinline__ void s2_sweep(SW& W, const int32_t* npq, int nq, cons
           s2_uniform(b);
           if (b.pp < 0) {
             b.tracei = ++W.tracectr;
-            b.score = kS2K;
+            if constexpr (SW::kLocalp) b.score = kS2K;
           }
           if (lane == i) mb = b;
         }
@@ -1400,6 +1420,9 @@ __device__ __forceinline__ void s2_sweep(SW& W, const int32_t* npq, int nq, cons
         bl = __ffsll((long long)ballot(lane < nh && sc == smax)) - 1;
         best_score = smax;
         best_hit = low + bl;
+      }
+      if constexpr (!SW::kMiddlep) {  // a new start for every hit (:3955-3980); root stays the hit's own position
+        if (best_hit < 0 && lane < nh) mb = {kS2K, (int)cm, -1, -1, kS2K, -1};
       }
       nskipped = 0;
       min_hits = 1000000;
@@ -1462,6 +1485,15 @@ __device__ __forceinline__ void s2_sweep(SW& W, const int32_t* npq, int nq, cons
         }
         best_score = bs;
         best_hit = bh;
+        if constexpr (!SW::kMiddlep) {  // a new start for every hit (:3955-3980)
+          if (bh < 0) {
+            for (int i = low + lane; i < high; i += 64) {
+              W.hits[qoff + i] = S2Hit{kS2K, (int)W.maps[qoff + i], -1, -1};
+              W.sc[qoff + i] = kS2K;
+            }
+            wave_sync();
+          }
+        }
         if (bh >= 0) {
           best_fhit = W.hits[qoff + bh].pred;
           best_consec = W.hits[qoff + bh].consec;
@@ -1810,7 +1842,7 @@ __global__ __launch_bounds__(64) void s2a_kernel(
   const double pct = (double)ncovered / (double)ql;
   if (T == 0) {
     R.status = kS2NoPositions;
-  } else if (ql > 150 && pct < 0.3 && ncovered < 200) {
+  } else if (P.kind == 0 && ql > 150 && pct < 0.3 && ncovered < 200) {  // (_one / _ends: totalpositions alone)
     R.status = kS2Coverage;
   } else {
     R.status = kS2Chained;
@@ -1827,7 +1859,7 @@ __global__ __launch_bounds__(64) void s2a_kernel(
   const uint32_t chrterm = P.plusp ? P.chrend : (P.chrhigh - P.chroffset) - P.chrstart;
   const uint32_t genomiclength = P.chrend - P.chrstart;
   int qstart, qend;
-  if (nd == 0) {
+  if (nd == 0 || P.kind != 0) {  // no diagonals; Stage2_compute_one / _ends: Diag_max_bounds (diag.c:894)
     fill_range(lane, minact, 0, ql - 1, [&](int) { return chrinit; });
     fill_range(lane, maxact, 0, ql - 1, [&](int) { return chrterm; });
     qstart = 0;
@@ -2145,7 +2177,7 @@ __global__ __launch_bounds__(64) void s2a_kernel(
 #endif
 // (the body of both instantiations: s2b_kernel, the default, and s2b_canon_kernel, which also takes the
 // MaxEnt tables)
-template <bool kCanon>
+template <bool kCanon, int kKind = 0>
 __device__ __forceinline__ void s2b_body(
     const DevStage2Problem* __restrict__ probs, const uint32_t* __restrict__ blocks, uint64_t nwords,
     const char* __restrict__ qseq, const char* __restrict__ quc, const gmapdp_oligo_result* __restrict__ ores,
@@ -2194,7 +2226,7 @@ __device__ __forceinline__ void s2b_body(
 #endif
   // ---- align_compute_scores_lookback: the sweep on lane 0 ----
   {
-    S2WT<kCanon> W;
+    S2WT<kCanon, kKind != 2, kKind != 2, kKind == 0> W;
     if constexpr (kCanon) {
       W.blocks = blocks;
       W.metab = metab;
@@ -2270,6 +2302,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GMAPDP_S2B_C
     const double* __restrict__ metab) {
   s2b_body<true>(probs, blocks, nwords, qseq, quc, ores, npos_all, map_all, table_all, diag_all, scratch, counters,
                  scratch_cap, results, paths_out, path_cap, pairs_out, pair_cap, metab);
+}
+
+// the sweeps of Stage2_compute_one (localp, middlep, no repetitive-position skipping) and Stage2_compute_ends
+// (neither localp nor middlep, no skipping): S2WT's three facts; short calls, so no register budget of their own
+__global__ __launch_bounds__(64) void s2b_one_kernel(
+    const DevStage2Problem* __restrict__ probs, const uint32_t* __restrict__ blocks, uint64_t nwords,
+    const char* __restrict__ qseq, const char* __restrict__ quc, const gmapdp_oligo_result* __restrict__ ores,
+    const int32_t* __restrict__ npos_all, const int32_t* __restrict__ map_all, const uint32_t* __restrict__ table_all,
+    const int32_t* __restrict__ diag_all, unsigned char* __restrict__ scratch, unsigned long long* __restrict__ counters,
+    unsigned long long scratch_cap, gmapdp_stage2_result* __restrict__ results, gmapdp_path* __restrict__ paths_out,
+    unsigned long long path_cap, gmapdp_path_pair* __restrict__ pairs_out, unsigned long long pair_cap) {
+  s2b_body<false, 1>(probs, blocks, nwords, qseq, quc, ores, npos_all, map_all, table_all, diag_all, scratch, counters,
+                     scratch_cap, results, paths_out, path_cap, pairs_out, pair_cap, nullptr);
+}
+__global__ __launch_bounds__(64) void s2b_ends_kernel(
+    const DevStage2Problem* __restrict__ probs, const uint32_t* __restrict__ blocks, uint64_t nwords,
+    const char* __restrict__ qseq, const char* __restrict__ quc, const gmapdp_oligo_result* __restrict__ ores,
+    const int32_t* __restrict__ npos_all, const int32_t* __restrict__ map_all, const uint32_t* __restrict__ table_all,
+    const int32_t* __restrict__ diag_all, unsigned char* __restrict__ scratch, unsigned long long* __restrict__ counters,
+    unsigned long long scratch_cap, gmapdp_stage2_result* __restrict__ results, gmapdp_path* __restrict__ paths_out,
+    unsigned long long path_cap, gmapdp_path_pair* __restrict__ pairs_out, unsigned long long pair_cap) {
+  s2b_body<false, 2>(probs, blocks, nwords, qseq, quc, ores, npos_all, map_all, table_all, diag_all, scratch, counters,
+                     scratch_cap, results, paths_out, path_cap, pairs_out, pair_cap, nullptr);
 }
 
 // traceback_one over the LDS link table, 8 B per hit: lql[i] = query position << 16 | a bit 15 set when
@@ -2404,7 +2459,11 @@ __device__ S2WalkOut s2_walk_wave(const uint32_t* lql, const uint32_t* map, int 
 // kModal: a cmet / atoi / ttoc context (convert_to_nucleotides outside STANDARD, stage2.c:5403-5452): every
 // pair's genome character is the real (unreduced) genome's, and a pair whose query character differs from
 // it carries ':' (AMBIGUOUS_COMP) instead of '|'.
-template <bool kLdsWalk, bool kModal>
+// kKind: 0 Stage2_compute; GMAPDP_S2X_ONE (1) / _ENDS (2): the path loop with max_nalignments 1 (the best cell
+// and every further cell of its score); ONE keeps the last path traced, with gap holders, its pairs 3' end first
+// (List_reverse(middle), stage2.c:6908); ENDS converts every path without gap holders and filters the lists by
+// Stage2pairs_filter_unique_ends (:6218); both add query_offset to the pairs' querypos.
+template <bool kLdsWalk, bool kModal, int kKind = 0>
 __global__ __launch_bounds__(64) void s2c_kernel(
     const DevStage2Problem* __restrict__ probs, const uint32_t* __restrict__ blocks, uint64_t nwords,
     const char* __restrict__ qseq, const char* __restrict__ quc, const gmapdp_oligo_result* __restrict__ ores,
@@ -2556,8 +2615,18 @@ __global__ __launch_bounds__(64) void s2c_kernel(
   for (int i = lane; i < nkeep; i += 64) cand[i] = slots[i];
   wave_sync();
   int npaths = 0;
-  while (npaths < nkeep && (npaths < kS2MaxNalignments || scs[cand[npaths]] == best)) npaths++;
+  constexpr int kMaxNalignments = kKind ? 1 : kS2MaxNalignments;  // (stage3.c:11382 / 15855 pass 1)
+  while (npaths < nkeep && (npaths < kMaxNalignments || scs[cand[npaths]] == best)) npaths++;
   R.npaths = npaths;
+  if constexpr (kKind == 1) {  // List_head(all_paths): paths are pushed, so the last cell the loop traced
+    if (npaths > 1) {
+      const int lastc = cand[npaths - 1];
+      wave_sync();
+      if (lane == 0) cand[0] = lastc;
+      wave_sync();
+      npaths = 1;
+    }
+  }
 
   S2_MARK(5);
   // ---- traceback_one per selected cell: length and extent of the converted list ----
@@ -2663,6 +2732,20 @@ __global__ __launch_bounds__(64) void s2c_kernel(
     }
     wave_sync();
   }
+  if constexpr (kKind != 0) {
+    // a path without pairs is no list (Stage2_compute_one's NULL middle, _ends' `pairs != NULL`); ENDS: when
+    // no list was eliminated only array[0] is kept (:6281-6283)
+    int any = 0, first = -1;
+    for (int i = 0; i < npaths; i++) {
+      if (pth[pord[i]].n == 0) continue;
+      if (first < 0) first = i;
+      any |= keep[i];
+    }
+    wave_sync();
+    for (int i = lane; i < npaths; i += 64)
+      if (pth[pord[i]].n == 0 || (kKind == 2 && !any && i != first)) keep[i] = 1;
+    wave_sync();
+  }
   int nres = 0;
   for (int i = 0; i < npaths; i++) nres += keep[i] ? 0 : 1;
   R.nresults = nres;
@@ -2723,6 +2806,7 @@ __global__ __launch_bounds__(64) void s2c_kernel(
         if (e < n) {
           int fill, gap;
           s2_entry_v(e, qp[k], gp[k], lqv[k], lgv[k], fill, gap);
+          if constexpr (kKind == 2) gap = 0;  // include_gapholders_p false
           cnt += gap + fill + 1;
         }
       }
@@ -2739,6 +2823,10 @@ __global__ __launch_bounds__(64) void s2c_kernel(
       return;
     }
     gmapdp_path_pair* dst = pairs_out + qb;
+    // record of generation index g (the order convert_to_nucleotides pushes: 3' end first): the list runs 5' end
+    // first; Stage2_compute_one returns it reversed
+    auto slot = [&](int g) { return kKind == 1 ? g : total - 1 - g; };
+    const int qoffs = kKind ? P.query_offset : 0;
     int gen = 0;
     for (int cb = 0; cb < n; cb += 64 * kC) {
       int qp[kC], gp[kC], lqv[kC], lgv[kC];
@@ -2763,6 +2851,7 @@ __global__ __launch_bounds__(64) void s2c_kernel(
         int cnt = 0, fill = 0, gap = 0;
         if (e < n) {
           s2_entry_v(e, qp[k], gp[k], lqv[k], lgv[k], fill, gap);
+          if constexpr (kKind == 2) gap = 0;
           cnt = gap + fill + 1;
         }
         const int incl = wave_incl_sum(cnt, lane);
@@ -2775,23 +2864,23 @@ __global__ __launch_bounds__(64) void s2c_kernel(
             rr.queryjump = (lqv[k] - 1 - qpos) - fill;
             rr.genomejump = (lgv[k] - 1 - gpos) - fill;
             rr.cdna = rr.comp = rr.genome = rr.genomealt = ' ';
-            dst[total - 1 - g++] = rr;
+            dst[slot(g++)] = rr;
           }
           for (int j = 0; j < fill; j++) {
             const int lq = qpos + fill - j, lg = gpos + fill - j;
             const char c = s2_genomic_nt(blocks, nwords, (uint32_t)lg, P.chroffset, P.chrhigh, plusp);
             gmapdp_path_pair rr;
-            rr.querypos = lq;
+            rr.querypos = lq + qoffs;
             rr.genomepos = lg;
             rr.queryjump = rr.genomejump = 0;
             rr.cdna = qs[lq];
             rr.comp = '|';
             if constexpr (kModal) rr.comp = qu[lq] == c ? '|' : ':';  // queryuc against the genome (:5405)
             rr.genome = rr.genomealt = c;
-            dst[total - 1 - g++] = rr;
+            dst[slot(g++)] = rr;
           }
           gmapdp_path_pair rr;
-          rr.querypos = qpos;
+          rr.querypos = qpos + qoffs;
           rr.genomepos = gpos;
           rr.queryjump = rr.genomejump = 0;
           rr.cdna = cq[k];
@@ -2805,7 +2894,7 @@ __global__ __launch_bounds__(64) void s2c_kernel(
             rr.comp = cq[k] == c ? '|' : ':';
             rr.genome = rr.genomealt = c;
           }
-          dst[total - 1 - g] = rr;
+          dst[slot(g)] = rr;
         }
         gen += __shfl(incl, 63, 64);
       }
@@ -2859,7 +2948,9 @@ hipError_t launch_s2c(int nproblems, hipStream_t stream, const DevStage2Problem*
                       unsigned char* scratch, unsigned long long* counters, unsigned long long scratch_cap,
                       gmapdp_stage2_result* results, gmapdp_path* paths, unsigned long long path_cap,
                       gmapdp_path_pair* pairs, unsigned long long pair_cap, bool modal, int phases,
-                      const double* canon_metab) {
+                      const double* canon_metab, int kind) {
+  // kind: the batch's DevStage2Problem.kind (0 Stage2_compute, GMAPDP_S2X_ONE / _ENDS): the sweep's and the
+  // path kernels' variant
   // canon_metab: the MaxEnt tables of a GMAPDP_S2_CANONICAL_MIDDLE batch (the sweep's canonical variant), else NULL
   void* args[] = {(void*)&probs, (void*)&blocks, (void*)&nwords, (void*)&qseq, (void*)&quc, (void*)&ores,
                   (void*)&npos, (void*)&map, (void*)&table, (void*)&diags, (void*)&scratch, (void*)&counters,
@@ -2887,7 +2978,10 @@ hipError_t launch_s2c(int nproblems, hipStream_t stream, const DevStage2Problem*
       const char* v = std::getenv("GMAPDP_S2B_LDS");
       return v ? (size_t)std::strtoull(v, nullptr, 10) : (size_t)0;
     }();
-    void* sweep = canon_metab ? reinterpret_cast<void*>(&s2b_canon_kernel) : reinterpret_cast<void*>(&s2b_kernel);
+    void* sweep = kind == 1   ? reinterpret_cast<void*>(&s2b_one_kernel)
+                  : kind == 2 ? reinterpret_cast<void*>(&s2b_ends_kernel)
+                  : canon_metab ? reinterpret_cast<void*>(&s2b_canon_kernel)
+                                : reinterpret_cast<void*>(&s2b_kernel);
     if (xlds > 64 * 1024) e = hipFuncSetAttribute(sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds);
     if (e == hipSuccess) e = hipLaunchKernel(sweep, dim3(nproblems), dim3(64), args, xlds, stream);
   }
@@ -2897,6 +2991,17 @@ hipError_t launch_s2c(int nproblems, hipStream_t stream, const DevStage2Problem*
                         : reinterpret_cast<void*>(&s2c_kernel<false, false>);
     void* rest = modal ? reinterpret_cast<void*>(&s2c_kernel<true, true>)
                        : reinterpret_cast<void*>(&s2c_kernel<true, false>);
+    if (kind == 1) {
+      heavy = modal ? reinterpret_cast<void*>(&s2c_kernel<false, true, 1>)
+                    : reinterpret_cast<void*>(&s2c_kernel<false, false, 1>);
+      rest = modal ? reinterpret_cast<void*>(&s2c_kernel<true, true, 1>)
+                   : reinterpret_cast<void*>(&s2c_kernel<true, false, 1>);
+    } else if (kind == 2) {
+      heavy = modal ? reinterpret_cast<void*>(&s2c_kernel<false, true, 2>)
+                    : reinterpret_cast<void*>(&s2c_kernel<false, false, 2>);
+      rest = modal ? reinterpret_cast<void*>(&s2c_kernel<true, true, 2>)
+                   : reinterpret_cast<void*>(&s2c_kernel<true, false, 2>);
+    }
     e = hipLaunchKernel(heavy, dim3(nproblems), dim3(64), args, 0, stream);
     if (e == hipSuccess)
       e = hipFuncSetAttribute(rest, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(8 * kS2cCap));

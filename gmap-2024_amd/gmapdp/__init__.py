@@ -121,6 +121,14 @@ class Stage2Problem(C.Structure):
 S2_CANONICAL_MIDDLE = 1  # GMAPDP_S2_CANONICAL_MIDDLE: gmap --cross-species
 
 
+class Stage2xProblem(C.Structure):
+    """gmapdp_stage2x_problem: Stage2Problem's fields, then kind and query_offset."""
+    _fields_ = Stage2Problem._fields_ + [("kind", C.c_int32), ("query_offset", C.c_int32)]
+
+
+S2X_ONE, S2X_ENDS = 1, 2  # GMAPDP_S2X_ONE / _ENDS: Stage2_compute_one / Stage2_compute_ends
+
+
 class Stage2Result(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("nresults", "npaths", "ncovered", "status", "diag_querystart",
                                           "diag_queryend", "path_offset", "npairs")]
@@ -162,6 +170,7 @@ OLIGO_RESULT_DTYPE = _struct_dtype(OligoResult)
 SCAN_RESULT_DTYPE = _struct_dtype(ScanResult)
 STAGE2_PROBLEM_DTYPE = _struct_dtype(Stage2Problem)
 STAGE2_RESULT_DTYPE = _struct_dtype(Stage2Result)
+STAGE2X_PROBLEM_DTYPE = _struct_dtype(Stage2xProblem)
 PATH_DTYPE = np.dtype([("pair_offset", "<i8"), ("npairs", "<i4"), ("pad_", "<i4")])
 PATH_PAIR_DTYPE = np.dtype([("querypos", "<i4"), ("genomepos", "<i4"), ("queryjump", "<i4"), ("genomejump", "<i4"),
                             ("cdna", "S1"), ("comp", "S1"), ("genome", "S1"), ("genomealt", "S1")])
@@ -215,6 +224,9 @@ def load_library(path=LIB_PATH):
         "gmapdp_stage2_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_size_t,
                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                           C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+        "gmapdp_stage2x_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_size_t,
+                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                           C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
         "gmapdp_pack_genome": (C.c_int, [C.c_char_p, C.c_uint64, C.c_void_p]),
         "gmapdp_set_genome": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64]),
         "gmapdp_single_gap_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -937,6 +949,65 @@ class Engine:
         calls = list(calls)
         probs, qbuf, qucbuf = self.build_stage2_batch(calls, cross_species)
         results, paths, pairs = self.stage2_batch_raw(probs, qbuf, qucbuf)
+        out = []
+        for r in results:
+            lists = []
+            for k in range(int(r["nresults"])):
+                pr = paths[int(r["path_offset"]) + k]
+                o, m = int(pr["pair_offset"]), int(pr["npairs"])
+                lst = []
+                for x in pairs[o:o + m]:
+                    gap = 1 if x["querypos"] == -1 and x["genomepos"] == -1 else 0
+                    lst.append((int(x["querypos"]), int(x["genomepos"]), int(x["queryjump"]), int(x["genomejump"]), 0,
+                                bytes(x["cdna"]) or b"\0", bytes(x["comp"]) or b"\0", bytes(x["genome"]) or b"\0",
+                                bytes(x["genomealt"]) or b"\0", gap))
+                lists.append(lst)
+            out.append((int(r["nresults"]), lists))
+        return out
+
+    # -- batched Stage2_compute_one / Stage2_compute_ends (stage 3's calls on a query segment) -------
+    @staticmethod
+    def build_stage2x_batch(calls, kind):
+        """calls: build_stage2_batch's dicts plus query_offset -> (problems, qbuf, qucbuf), every call of
+        `kind` (S2X_ONE or S2X_ENDS)."""
+        calls = list(calls)
+        base, qbuf, qucbuf = Engine.build_stage2_batch(calls)
+        probs = np.zeros(len(calls), dtype=STAGE2X_PROBLEM_DTYPE)
+        for k in STAGE2_PROBLEM_DTYPE.names:
+            probs[k] = base[k]
+        probs["kind"] = kind
+        probs["query_offset"] = [int(p.get("query_offset", 0)) for p in calls]
+        return probs, qbuf, qucbuf
+
+    def stage2x_batch_raw(self, probs, qbuf, qucbuf, path_cap=None, pair_cap=None):
+        """gmapdp_stage2x_batch -> (results, paths, pairs).  With path_cap / pair_cap given the call is made
+        once with arenas of those sizes and GMAPDP_ESPACE comes back as (-6, paths needed, pairs needed)."""
+        n = len(probs)
+        results = np.zeros(n, dtype=STAGE2_RESULT_DTYPE)
+        fixed = path_cap is not None or pair_cap is not None
+        pcap = 4 * n + 16 if path_cap is None else path_cap
+        qcap = 2 * len(qucbuf) + 64 if pair_cap is None else pair_cap
+        while True:
+            paths = np.zeros(max(pcap, 1), dtype=PATH_DTYPE)
+            pairs = np.zeros(max(qcap, 1), dtype=PATH_PAIR_DTYPE)
+            pn, qn = C.c_size_t(), C.c_size_t()
+            rc = self.lib.gmapdp_stage2x_batch(self.h, probs.ctypes.data, n, qbuf, qucbuf, len(qucbuf),
+                                               results.ctypes.data, paths.ctypes.data, pcap, pairs.ctypes.data,
+                                               qcap, C.byref(pn), C.byref(qn))
+            if rc == -6:  # GMAPDP_ESPACE
+                if fixed:
+                    return rc, pn.value, qn.value
+                pcap, qcap = max(pcap, pn.value), max(qcap, qn.value)
+                continue
+            self._check(rc, "gmapdp_stage2x_batch")
+            return results, paths[:pn.value], pairs[:qn.value]
+
+    def stage2x_batch(self, calls, kind):
+        """Per call (number of returned lists, [pair-key list per list, in the list's order]) -- stage2_batch's
+        format.  kind: S2X_ONE (Stage2_compute_one: zero or one list, 3' end first) or S2X_ENDS
+        (Stage2_compute_ends after Stage2pairs_filter_unique_ends)."""
+        probs, qbuf, qucbuf = self.build_stage2x_batch(calls, kind)
+        results, paths, pairs = self.stage2x_batch_raw(probs, qbuf, qucbuf)
         out = []
         for r in results:
             lists = []
