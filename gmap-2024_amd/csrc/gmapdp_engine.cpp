@@ -3823,8 +3823,8 @@ static int s2_batch_core(gmapdp_ctx* ctx, int n, std::vector<gmapdp_oligo_proble
   }
 }
 
-// Stage2_compute_one / Stage2_compute_ends (stage2.c:6754 / 7087) as stage 3 calls them: the seeding with the
-// minor oligoindex, then the chaining kernels' variants for the batch's kind (launch_s2c).
+// Stage2_compute_one / Stage2_compute_ends / Stage2_compute_starts (stage2.c:6754 / 7087 / 6914) as stage 3 calls
+// them: the seeding with the minor oligoindex, then the chaining kernels' variants for the batch's kind (launch_s2c).
 extern "C" int gmapdp_stage2x_batch(gmapdp_ctx* ctx, const gmapdp_stage2x_problem* problems, int n, const char* qseq,
                                     const char* qseq_uc, size_t qbytes, gmapdp_stage2_result* results,
                                     gmapdp_path* paths, size_t path_cap, gmapdp_path_pair* pairs, size_t pair_cap,
@@ -3844,12 +3844,13 @@ extern "C" int gmapdp_stage2x_batch(gmapdp_ctx* ctx, const gmapdp_stage2x_proble
   const int kind = problems[0].kind;
   for (int i = 0; i < n; i++) {
     const gmapdp_stage2x_problem& p = problems[i];
-    if (p.kind != GMAPDP_S2X_ONE && p.kind != GMAPDP_S2X_ENDS)
-      return bad(ctx, "stage 2x: kind is neither GMAPDP_S2X_ONE nor GMAPDP_S2X_ENDS");
-    if (p.kind != kind) return bad(ctx, "stage 2x: one batch takes one kind (GMAPDP_S2X_ONE and _ENDS are mixed)");
+    if (p.kind != GMAPDP_S2X_ONE && p.kind != GMAPDP_S2X_ENDS && p.kind != GMAPDP_S2X_STARTS)
+      return bad(ctx, "stage 2x: kind is none of GMAPDP_S2X_ONE, _ENDS and _STARTS");
+    if (p.kind != kind)
+      return bad(ctx, "stage 2x: one batch takes one kind (GMAPDP_S2X_ONE, _ENDS and _STARTS are not mixed)");
     if (p.flags != 0) return bad(ctx, "stage 2x: flags must be 0 (no cross-species scoring for these calls)");
     if (p.maxintronlen < 0) return bad(ctx, "stage 2x: negative maxintronlen");
-    // (minor 1: both calls take oligoindices_minor, stage3.c:11392 / 15853)
+    // (minor 1: all three calls take oligoindices_minor, stage3.c:11392 / 15853 / 15959)
     op[i] = gmapdp_oligo_problem{p.qoff, p.querylength, p.chrstart, p.chrend, p.chroffset, p.chrhigh,
                                  p.plusp ? 1 : 0, 1};
     dp[i] = DevStage2Problem{p.qoff, p.querylength, p.chrstart, p.chrend, p.chroffset, p.chrhigh, p.plusp ? 1 : 0,

@@ -198,7 +198,8 @@ struct DevStage2Problem {
   uint32_t maxintronlen;
   int32_t index;          // the problem's index in the batch (seeding result and stage-2 result slot)
   int64_t scratch_offset; // byte offset of the problem's chaining scratch (s2_scratch, sized from the seeding)
-  int32_t kind;           // 0 Stage2_compute; GMAPDP_S2X_ONE / _ENDS: Stage2_compute_one / _ends (one per batch)
+  int32_t kind;           // 0 Stage2_compute; GMAPDP_S2X_ONE / _ENDS / _STARTS: Stage2_compute_one / _ends / _starts
+                          // (one per batch)
   int32_t query_offset;   // added to every pair's querypos (kind != 0)
 };
 

@@ -1749,14 +1749,21 @@ __global__ __launch_bounds__(kS2OrderThreads) void s2_order_kernel(const DevStag
   }
 }
 
-__global__ __launch_bounds__(64) void s2a_kernel(
+// kMirror: a Stage2_compute_starts call (GMAPDP_S2X_STARTS).  Its sweep, align_compute_scores_lookforward
+// (stage2.c:4610), is the lookback sweep on the mirrored call: query position q -> nq - 1 - q, hit h of n ->
+// n - 1 - h, chrpos p -> M - p with M = chrinit + chrterm (every hit lies in [chrinit, chrterm], so M - p does
+// too: ascending within a mirrored position, below 2^31).  In the flat hit index that is i -> N - 1 - i.  The
+// layout below writes the mirrored call -- maps, off[], rmap, the first swept position's range, and the
+// per-position hit counts (npq' in the maxactive array, which nothing reads after this kernel) -- and
+// s2b_starts_kernel runs the ENDS sweep on it unchanged; s2c_kernel<.., .., 3> un-mirrors.
+template <bool kMirror>
+__device__ __forceinline__ void s2a_body(
     const DevStage2Problem* __restrict__ probs, const uint32_t* __restrict__ blocks, uint64_t nwords,
     const char* __restrict__ qseq, const char* __restrict__ quc, const gmapdp_oligo_result* __restrict__ ores,
     const int32_t* __restrict__ npos_all, const int32_t* __restrict__ map_all, const uint32_t* __restrict__ table_all,
     const int32_t* __restrict__ diag_all, unsigned char* __restrict__ scratch, unsigned long long* __restrict__ counters,
     unsigned long long scratch_cap, gmapdp_stage2_result* __restrict__ results, gmapdp_path* __restrict__ paths_out,
-    unsigned long long path_cap, gmapdp_path_pair* __restrict__ pairs_out, unsigned long long pair_cap) {
-  __shared__ int sh[8];
+    unsigned long long path_cap, gmapdp_path_pair* __restrict__ pairs_out, unsigned long long pair_cap, int* sh) {
   const int lane = threadIdx.x;
   const int pos = s2_problem(counters);
   const DevStage2Problem P = probs[pos];
@@ -2064,10 +2071,15 @@ __global__ __launch_bounds__(64) void s2a_kernel(
   uint32_t* rmapa = reinterpret_cast<uint32_t*>(diff);  // (the coverage is done with diff)
   const uint32_t* __restrict__ tb = table_all + O.table_offset;  // (mappings relative to the call's table)
   wave_sync();
+  // (kMirror: q runs over the mirrored positions, qr the real one whose seeding is read; qstart 0, qend ql - 1)
+  const uint32_t mirror = chrinit + chrterm;
+  int* npm = reinterpret_cast<int*>(maxact);  // kMirror: the hit counts in mirrored order, for the sweep
+  (void)mirror; (void)npm;
   int q0 = -1;
   for (int cb = qstart & ~63; cb <= qend && q0 < 0; cb += 64) {
     const int q = cb + lane;
-    const uint64_t m = ballot(q >= qstart && q <= qend && q < nq && npq[q] > 0);
+    const int qr = kMirror ? nq - 1 - q : q;
+    const uint64_t m = ballot(q >= qstart && q <= qend && q < nq && npq[qr] > 0);
     if (m) q0 = cb + __ffsll((long long)m) - 1;
   }
   // chromosome positions past 2^31 (Pairpool_push would drop them: outside the domain) are looked for among
@@ -2079,10 +2091,12 @@ __global__ __launch_bounds__(64) void s2a_kernel(
   int wk = 0;
   for (int cb = 0; cb < ql; cb += 64) {
     const int q = cb + lane;
-    const int v = q < nq ? npq[q] : 0;
-    const int mq = v > 0 ? mpq[q] : 0;
+    const int qr = kMirror ? nq - 1 - q : q;
+    const int v = q < nq ? npq[qr] : 0;
+    const int mq = v > 0 ? mpq[qr] : 0;
     const bool act = q <= qend && v > 0;
-    const uint32_t qmn = act ? minact[q] : 0u, qmx0 = act ? maxact[q] : 0u;
+    // (kMirror: Diag_max_bounds' constants; maxact is being overwritten with npm)
+    const uint32_t qmn = act ? (kMirror ? chrinit : minact[q]) : 0u, qmx0 = act ? (kMirror ? chrterm : maxact[q]) : 0u;
     const uint32_t qmx = (qmn > 0 && qmx0 < qmn - 1) ? qmn - 1 : qmx0;
     if (scan_big && v > 0) big |= (tb[mq + v - 1] >= 0x80000000u);
     int low = 0, high = 0;
@@ -2122,10 +2136,11 @@ __global__ __launch_bounds__(64) void s2a_kernel(
     // the sweep's work: a position's lookbacks grow with the hits of its range (each one beyond the first
     // a full lookback); a diagonal far from the others widens those ranges over the gap
     if (q >= qstart && q <= qend && high > low) wk += 1 + 4 * (high - low - 1);
+    if constexpr (kMirror) rmap = high > low ? mirror - tb[mq + high - 1] : 0u;  // the mirrored range's first hit
     int c = high - low, first_hit = mq + low;
     if (q == q0) {  // (act: q0 <= qend and it has hits)
-      fp[0] = low;
-      fp[1] = high;
+      fp[0] = kMirror ? v - high : low;
+      fp[1] = kMirror ? v - low : high;
       c = v;
       first_hit = mq;
     }
@@ -2134,6 +2149,7 @@ __global__ __launch_bounds__(64) void s2a_kernel(
     if (q < ql) {
       off[q] = o;
       rmapa[q] = rmap;
+      if constexpr (kMirror) npm[q] = v;
     }
     const int hend = __shfl(incl, 63, 64);
     for (int base = carry; base < hend; base += 64) {
@@ -2145,7 +2161,13 @@ __global__ __launch_bounds__(64) void s2a_kernel(
         if (oj <= h) j += st;
       }
       const int oq = __shfl(o, j, 64), fj = __shfl(first_hit, j, 64);
-      if (h < hend) {
+      if constexpr (kMirror) {  // the position's laid-out hits last first, each M - chrpos
+        const int cj = __shfl(c, j, 64);
+        if (h < hend) {
+          mapsa[h] = mirror - tb[fj + (cj - 1 - (h - oq))];
+          sca[h] = 0;
+        }
+      } else if (h < hend) {
         mapsa[h] = tb[fj + (h - oq)];
         sca[h] = 0;
       }
@@ -2169,6 +2191,30 @@ __global__ __launch_bounds__(64) void s2a_kernel(
   if (lane == 0) work[pos] = wk;
 
   if (lane == 0) results[P.index] = R;  // status 2 with the query bounds: the sweep and the paths follow
+}
+
+__global__ __launch_bounds__(64) void s2a_kernel(
+    const DevStage2Problem* __restrict__ probs, const uint32_t* __restrict__ blocks, uint64_t nwords,
+    const char* __restrict__ qseq, const char* __restrict__ quc, const gmapdp_oligo_result* __restrict__ ores,
+    const int32_t* __restrict__ npos_all, const int32_t* __restrict__ map_all, const uint32_t* __restrict__ table_all,
+    const int32_t* __restrict__ diag_all, unsigned char* __restrict__ scratch, unsigned long long* __restrict__ counters,
+    unsigned long long scratch_cap, gmapdp_stage2_result* __restrict__ results, gmapdp_path* __restrict__ paths_out,
+    unsigned long long path_cap, gmapdp_path_pair* __restrict__ pairs_out, unsigned long long pair_cap) {
+  __shared__ int sh[8];
+  s2a_body<false>(probs, blocks, nwords, qseq, quc, ores, npos_all, map_all, table_all, diag_all, scratch, counters,
+                  scratch_cap, results, paths_out, path_cap, pairs_out, pair_cap, sh);
+}
+// the mirrored layout of a GMAPDP_S2X_STARTS batch, in a kernel of its own so that s2a_kernel keeps its registers
+__global__ __launch_bounds__(64) void s2a_starts_kernel(
+    const DevStage2Problem* __restrict__ probs, const uint32_t* __restrict__ blocks, uint64_t nwords,
+    const char* __restrict__ qseq, const char* __restrict__ quc, const gmapdp_oligo_result* __restrict__ ores,
+    const int32_t* __restrict__ npos_all, const int32_t* __restrict__ map_all, const uint32_t* __restrict__ table_all,
+    const int32_t* __restrict__ diag_all, unsigned char* __restrict__ scratch, unsigned long long* __restrict__ counters,
+    unsigned long long scratch_cap, gmapdp_stage2_result* __restrict__ results, gmapdp_path* __restrict__ paths_out,
+    unsigned long long path_cap, gmapdp_path_pair* __restrict__ pairs_out, unsigned long long pair_cap) {
+  __shared__ int sh[8];
+  s2a_body<true>(probs, blocks, nwords, qseq, quc, ores, npos_all, map_all, table_all, diag_all, scratch, counters,
+                 scratch_cap, results, paths_out, path_cap, pairs_out, pair_cap, sh);
 }
 
 // the lookback sweep (align_compute_scores_lookback) of the calls s2a_kernel left chained
@@ -2226,7 +2272,7 @@ __device__ __forceinline__ void s2b_body(
 #endif
   // ---- align_compute_scores_lookback: the sweep on lane 0 ----
   {
-    S2WT<kCanon, kKind != 2, kKind != 2, kKind == 0> W;
+    S2WT<kCanon, kKind < 2, kKind < 2, kKind == 0> W;  // (kind 3, STARTS: ENDS' facts on the mirrored call)
     if constexpr (kCanon) {
       W.blocks = blocks;
       W.metab = metab;
@@ -2253,7 +2299,9 @@ __device__ __forceinline__ void s2b_body(
     W.splicingp = P.splicingp;
     W.lane = lane;
     W.maxintronlen = P.maxintronlen;
-    s2_sweep(W, npq, nq, reinterpret_cast<const int*>(S + so.lh), reinterpret_cast<const uint32_t*>(diff), qstart,
+    // (kind 3: the hit counts in mirrored order, which s2a_starts_kernel left in the maxactive array)
+    const int32_t* npw = kKind == 3 ? reinterpret_cast<const int32_t*>(maxact) : npq;
+    s2_sweep(W, npw, nq, reinterpret_cast<const int*>(S + so.lh), reinterpret_cast<const uint32_t*>(diff), qstart,
              qend);  // q0's range / rmap (s2a_kernel)
     if constexpr (kCanon) {
       for (int f = 0; f < 8; f++) {
@@ -2324,6 +2372,17 @@ __global__ __launch_bounds__(64) void s2b_ends_kernel(
     unsigned long long scratch_cap, gmapdp_stage2_result* __restrict__ results, gmapdp_path* __restrict__ paths_out,
     unsigned long long path_cap, gmapdp_path_pair* __restrict__ pairs_out, unsigned long long pair_cap) {
   s2b_body<false, 2>(probs, blocks, nwords, qseq, quc, ores, npos_all, map_all, table_all, diag_all, scratch, counters,
+                     scratch_cap, results, paths_out, path_cap, pairs_out, pair_cap, nullptr);
+}
+// Stage2_compute_starts: align_compute_scores_lookforward as the ENDS sweep over s2a_starts_kernel's mirrored layout
+__global__ __launch_bounds__(64) void s2b_starts_kernel(
+    const DevStage2Problem* __restrict__ probs, const uint32_t* __restrict__ blocks, uint64_t nwords,
+    const char* __restrict__ qseq, const char* __restrict__ quc, const gmapdp_oligo_result* __restrict__ ores,
+    const int32_t* __restrict__ npos_all, const int32_t* __restrict__ map_all, const uint32_t* __restrict__ table_all,
+    const int32_t* __restrict__ diag_all, unsigned char* __restrict__ scratch, unsigned long long* __restrict__ counters,
+    unsigned long long scratch_cap, gmapdp_stage2_result* __restrict__ results, gmapdp_path* __restrict__ paths_out,
+    unsigned long long path_cap, gmapdp_path_pair* __restrict__ pairs_out, unsigned long long pair_cap) {
+  s2b_body<false, 3>(probs, blocks, nwords, qseq, quc, ores, npos_all, map_all, table_all, diag_all, scratch, counters,
                      scratch_cap, results, paths_out, path_cap, pairs_out, pair_cap, nullptr);
 }
 
@@ -2463,6 +2522,14 @@ __device__ S2WalkOut s2_walk_wave(const uint32_t* lql, const uint32_t* map, int 
 // and every further cell of its score); ONE keeps the last path traced, with gap holders, its pairs 3' end first
 // (List_reverse(middle), stage2.c:6908); ENDS converts every path without gap holders and filters the lists by
 // Stage2pairs_filter_unique_ends (:6218); both add query_offset to the pairs' querypos.
+// GMAPDP_S2X_STARTS (3), Stage2_compute_starts: the link records are those of the mirrored call (s2a_body).  The
+// cells' keys are taken back to the real call (query position nq - 1 - q', root M - root' -- 0 stays the 0 the
+// reference leaves in the first swept position's links -- and the hit order reversed), so get_cells_fwd's
+// comparators see what the reference's see.  The walks follow the links as they are: in the real call from the
+// cell towards the 3' end, pruning at the walk's start.  Their entries are then reversed and un-mirrored, which
+// is the list convert_to_nucleotides receives (3'-most hit first); each list is written 3' end first
+// (List_reverse(pairs), :7040), without gap holders, and the lists go through Stage2pairs_filter_unique_starts
+// (:6114: chrend descending, then chrstart descending).
 template <bool kLdsWalk, bool kModal, int kKind = 0>
 __global__ __launch_bounds__(64) void s2c_kernel(
     const DevStage2Problem* __restrict__ probs, const uint32_t* __restrict__ blocks, uint64_t nwords,
@@ -2509,6 +2576,10 @@ __global__ __launch_bounds__(64) void s2c_kernel(
   if (s2c_lds_class(T, off[ql], nq) != kLdsWalk) return;  // the other launch's call
   S2_MARK(12);
   const int qstart = R.diag_querystart, qend = R.diag_queryend;
+  // kind 3: M of the mirrored layout (s2a_body: chrinit + chrterm)
+  const uint32_t mirror = (P.plusp ? P.chrstart : (uint32_t)((P.chrhigh - P.chroffset) - P.chrend)) +
+                          (P.plusp ? P.chrend : (uint32_t)((P.chrhigh - P.chroffset) - P.chrstart));
+  (void)mirror;
   // ---- get_cells_fwd + the path loop: cells within FINAL_SCORE_TOLERANCE of the best, each the best
   // of its root position, in (score desc, root asc, querypos desc, hit asc) order ----
   // one pass over the scores: the hits within the tolerance of the running best (a superset of those
@@ -2564,6 +2635,10 @@ __global__ __launch_bounds__(64) void s2c_kernel(
         keep[s] = sc;
         cq[s] = s2_hit_pos(off, ql, gi);
         croot[s] = hits[gi].root;
+        if constexpr (kKind == 3) {
+          cq[s] = nq - 1 - cq[s];
+          croot[s] = croot[s] == 0 ? 0 : (int)(mirror - (uint32_t)croot[s]);
+        }
         slots[s] = s;
       }
       n2 += __popcll(m);
@@ -2579,7 +2654,7 @@ __global__ __launch_bounds__(64) void s2c_kernel(
     if (croot[a] != croot[b]) return croot[a] < croot[b];
     if (keep[a] != keep[b]) return keep[a] > keep[b];
     if (cq[a] != cq[b]) return cq[a] > cq[b];
-    return cand[a] < cand[b];
+    return kKind == 3 ? cand[a] > cand[b] : cand[a] < cand[b];  // (kind 3: the real hit order is the reverse)
   });
   int nkeep = 0, gcarry = 0;
   for (int cb = 0; cb < ncand; cb += 64) {
@@ -2608,7 +2683,7 @@ __global__ __launch_bounds__(64) void s2c_kernel(
     if (keep[a] != keep[b]) return keep[a] > keep[b];
     if (croot[a] != croot[b]) return croot[a] < croot[b];
     if (cq[a] != cq[b]) return cq[a] > cq[b];
-    return cand[a] < cand[b];
+    return kKind == 3 ? cand[a] > cand[b] : cand[a] < cand[b];  // (kind 3: the real hit order is the reverse)
   });
   for (int i = lane; i < nkeep; i += 64) slots[i] = cand[sorted[i]];
   wave_sync();
@@ -2672,6 +2747,21 @@ __global__ __launch_bounds__(64) void s2c_kernel(
   // a single selected cell is the single result (Stage2_filter_unique keeps it): its walk records the
   // entries convert_to_nucleotides needs, and the second walk below is skipped
   const bool single = npaths == 1;
+  // kind 3: a walk's n entries (mirrored, the cell's first) to the real call's, 3'-most hit first; lane e takes the
+  // entries e and n - 1 - e
+  auto unmirror = [&](int n) {
+    wave_sync();
+    for (int e = lane; 2 * e < n; e += 64) {
+      const int f = n - 1 - e;
+      const int qa = pathq[e], ha = pathh[e], qb = pathq[f], hb = pathh[f];
+      pathq[e] = nq - 1 - qb;
+      pathh[e] = (int)(mirror - (uint32_t)hb);
+      pathq[f] = nq - 1 - qa;
+      pathh[f] = (int)(mirror - (uint32_t)ha);
+    }
+    wave_sync();
+  };
+  (void)unmirror;
   for (int p = 0; p < npaths; p++) {
     const int cell = s2_u(cand[p]);
     int n = 0, top = -1, bottom = -1;
@@ -2692,22 +2782,34 @@ __global__ __launch_bounds__(64) void s2c_kernel(
         n++;
       });
     }
+    if constexpr (kKind == 3) {
+      if (single) unmirror(s2_u(n));
+    }
     if (lane == 0) {
       S2Path r;
       r.cell = cell;
       r.n = n;
       r.start = n ? (lds_walk ? lmap[bottom] : maps[bottom]) : 0u;
       r.end = n ? (lds_walk ? lmap[top] : maps[top]) + (uint32_t)(kS2K - 1) : 0u;
+      if constexpr (kKind == 3) {  // the walk's first node is the real call's 5'-most, its last the 3'-most
+        r.start = n ? mirror - (lds_walk ? lmap[top] : maps[top]) : 0u;
+        r.end = n ? mirror - (lds_walk ? lmap[bottom] : maps[bottom]) + (uint32_t)(kS2K - 1) : 0u;
+      }
       pth[p] = r;
     }
   }
   wave_sync();
 
   // ---- Stage2_filter_unique: stable sort by (start, end), drop each path overlapping an earlier one ----
+  // (a path without entries has start = end = 0; it is no list, and below it neither counts as eliminated nor is kept)
   int* pord = cand;  // the selected cells live on in pth[].cell
   for (int i = lane; i < npaths; i += 64) keep[i] = i;
   wave_sync();
   wave_sort(lane, npaths, keep, pord, sbuf, [&](int a, int b) {
+    if constexpr (kKind == 3) {  // stage2pairs_start_cmp (:5773): chrend descending, then chrstart descending
+      if (pth[a].end != pth[b].end) return pth[a].end > pth[b].end;
+      return pth[a].start > pth[b].start;
+    }
     if (pth[a].start != pth[b].start) return pth[a].start < pth[b].start;
     return pth[a].end < pth[b].end;
   });
@@ -2733,8 +2835,8 @@ __global__ __launch_bounds__(64) void s2c_kernel(
     wave_sync();
   }
   if constexpr (kKind != 0) {
-    // a path without pairs is no list (Stage2_compute_one's NULL middle, _ends' `pairs != NULL`); ENDS: when
-    // no list was eliminated only array[0] is kept (:6281-6283)
+    // a path without pairs is no list (Stage2_compute_one's NULL middle, _ends' `pairs != NULL`, _starts' `path !=
+    // NULL`); ENDS / STARTS: when no list was eliminated only array[0] is kept (:6281-6283 / :6177-6179)
     int any = 0, first = -1;
     for (int i = 0; i < npaths; i++) {
       if (pth[pord[i]].n == 0) continue;
@@ -2743,7 +2845,7 @@ __global__ __launch_bounds__(64) void s2c_kernel(
     }
     wave_sync();
     for (int i = lane; i < npaths; i += 64)
-      if (pth[pord[i]].n == 0 || (kKind == 2 && !any && i != first)) keep[i] = 1;
+      if (pth[pord[i]].n == 0 || (kKind >= 2 && !any && i != first)) keep[i] = 1;
     wave_sync();
   }
   int nres = 0;
@@ -2785,6 +2887,9 @@ __global__ __launch_bounds__(64) void s2c_kernel(
       }
     }
     wave_sync();
+    if constexpr (kKind == 3) {
+      if (!single) unmirror(n);
+    }
     // records per entry in generation (prepend) order: [gap holder], fills, the observed pair.
     // Four 64-entry chunks per step, their loads issued together (the entries are in L2 scratch).
     constexpr int kC = 4;
@@ -2806,7 +2911,7 @@ __global__ __launch_bounds__(64) void s2c_kernel(
         if (e < n) {
           int fill, gap;
           s2_entry_v(e, qp[k], gp[k], lqv[k], lgv[k], fill, gap);
-          if constexpr (kKind == 2) gap = 0;  // include_gapholders_p false
+          if constexpr (kKind >= 2) gap = 0;  // include_gapholders_p false
           cnt += gap + fill + 1;
         }
       }
@@ -2825,7 +2930,7 @@ __global__ __launch_bounds__(64) void s2c_kernel(
     gmapdp_path_pair* dst = pairs_out + qb;
     // record of generation index g (the order convert_to_nucleotides pushes: 3' end first): the list runs 5' end
     // first; Stage2_compute_one returns it reversed
-    auto slot = [&](int g) { return kKind == 1 ? g : total - 1 - g; };
+    auto slot = [&](int g) { return (kKind == 1 || kKind == 3) ? g : total - 1 - g; };
     const int qoffs = kKind ? P.query_offset : 0;
     int gen = 0;
     for (int cb = 0; cb < n; cb += 64 * kC) {
@@ -2851,7 +2956,7 @@ __global__ __launch_bounds__(64) void s2c_kernel(
         int cnt = 0, fill = 0, gap = 0;
         if (e < n) {
           s2_entry_v(e, qp[k], gp[k], lqv[k], lgv[k], fill, gap);
-          if constexpr (kKind == 2) gap = 0;
+          if constexpr (kKind >= 2) gap = 0;
           cnt = gap + fill + 1;
         }
         const int incl = wave_incl_sum(cnt, lane);
@@ -2949,8 +3054,8 @@ hipError_t launch_s2c(int nproblems, hipStream_t stream, const DevStage2Problem*
                       gmapdp_stage2_result* results, gmapdp_path* paths, unsigned long long path_cap,
                       gmapdp_path_pair* pairs, unsigned long long pair_cap, bool modal, int phases,
                       const double* canon_metab, int kind) {
-  // kind: the batch's DevStage2Problem.kind (0 Stage2_compute, GMAPDP_S2X_ONE / _ENDS): the sweep's and the
-  // path kernels' variant
+  // kind: the batch's DevStage2Problem.kind (0 Stage2_compute, GMAPDP_S2X_ONE / _ENDS / _STARTS): the sweep's and
+  // the path kernels' variant; STARTS also the layout's (s2a_starts_kernel)
   // canon_metab: the MaxEnt tables of a GMAPDP_S2_CANONICAL_MIDDLE batch (the sweep's canonical variant), else NULL
   void* args[] = {(void*)&probs, (void*)&blocks, (void*)&nwords, (void*)&qseq, (void*)&quc, (void*)&ores,
                   (void*)&npos, (void*)&map, (void*)&table, (void*)&diags, (void*)&scratch, (void*)&counters,
@@ -2964,7 +3069,8 @@ hipError_t launch_s2c(int nproblems, hipStream_t stream, const DevStage2Problem*
     void* oargs0[] = {(void*)&probs, (void*)&nproblems, (void*)&ores, (void*)&counters, (void*)&nowork};
     e = hipLaunchKernel(reinterpret_cast<void*>(&s2_order_kernel), dim3(1), dim3(kS2OrderThreads), oargs0, 0, stream);
     if (e == hipSuccess)
-      e = hipLaunchKernel(reinterpret_cast<void*>(&s2a_kernel), dim3(nproblems), dim3(64), args, 0, stream);
+      e = hipLaunchKernel(kind == 3 ? reinterpret_cast<void*>(&s2a_starts_kernel) : reinterpret_cast<void*>(&s2a_kernel),
+                          dim3(nproblems), dim3(64), args, 0, stream);
     // the sweep (and s2c) heaviest first by s2a's work estimate
     const int* work = reinterpret_cast<const int*>(counters + 4) + nproblems;
     void* oargs1[] = {(void*)&probs, (void*)&nproblems, (void*)&ores, (void*)&counters, (void*)&work};
@@ -2980,6 +3086,7 @@ hipError_t launch_s2c(int nproblems, hipStream_t stream, const DevStage2Problem*
     }();
     void* sweep = kind == 1   ? reinterpret_cast<void*>(&s2b_one_kernel)
                   : kind == 2 ? reinterpret_cast<void*>(&s2b_ends_kernel)
+                  : kind == 3 ? reinterpret_cast<void*>(&s2b_starts_kernel)
                   : canon_metab ? reinterpret_cast<void*>(&s2b_canon_kernel)
                                 : reinterpret_cast<void*>(&s2b_kernel);
     if (xlds > 64 * 1024) e = hipFuncSetAttribute(sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds);
@@ -3001,6 +3108,11 @@ hipError_t launch_s2c(int nproblems, hipStream_t stream, const DevStage2Problem*
                     : reinterpret_cast<void*>(&s2c_kernel<false, false, 2>);
       rest = modal ? reinterpret_cast<void*>(&s2c_kernel<true, true, 2>)
                    : reinterpret_cast<void*>(&s2c_kernel<true, false, 2>);
+    } else if (kind == 3) {
+      heavy = modal ? reinterpret_cast<void*>(&s2c_kernel<false, true, 3>)
+                    : reinterpret_cast<void*>(&s2c_kernel<false, false, 3>);
+      rest = modal ? reinterpret_cast<void*>(&s2c_kernel<true, true, 3>)
+                   : reinterpret_cast<void*>(&s2c_kernel<true, false, 3>);
     }
     e = hipLaunchKernel(heavy, dim3(nproblems), dim3(64), args, 0, stream);
     if (e == hipSuccess)

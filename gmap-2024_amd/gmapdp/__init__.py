@@ -126,7 +126,7 @@ class Stage2xProblem(C.Structure):
     _fields_ = Stage2Problem._fields_ + [("kind", C.c_int32), ("query_offset", C.c_int32)]
 
 
-S2X_ONE, S2X_ENDS = 1, 2  # GMAPDP_S2X_ONE / _ENDS: Stage2_compute_one / Stage2_compute_ends
+S2X_ONE, S2X_ENDS, S2X_STARTS = 1, 2, 3  # GMAPDP_S2X_ONE / _ENDS / _STARTS: Stage2_compute_one / _ends / _starts
 
 
 class Stage2Result(C.Structure):
@@ -965,11 +965,11 @@ class Engine:
             out.append((int(r["nresults"]), lists))
         return out
 
-    # -- batched Stage2_compute_one / Stage2_compute_ends (stage 3's calls on a query segment) -------
+    # -- batched Stage2_compute_one / _ends / _starts (stage 3's calls on a query segment) -------
     @staticmethod
     def build_stage2x_batch(calls, kind):
         """calls: build_stage2_batch's dicts plus query_offset -> (problems, qbuf, qucbuf), every call of
-        `kind` (S2X_ONE or S2X_ENDS)."""
+        `kind` (S2X_ONE, S2X_ENDS or S2X_STARTS)."""
         calls = list(calls)
         base, qbuf, qucbuf = Engine.build_stage2_batch(calls)
         probs = np.zeros(len(calls), dtype=STAGE2X_PROBLEM_DTYPE)
@@ -1004,8 +1004,9 @@ class Engine:
 
     def stage2x_batch(self, calls, kind):
         """Per call (number of returned lists, [pair-key list per list, in the list's order]) -- stage2_batch's
-        format.  kind: S2X_ONE (Stage2_compute_one: zero or one list, 3' end first) or S2X_ENDS
-        (Stage2_compute_ends after Stage2pairs_filter_unique_ends)."""
+        format.  kind: S2X_ONE (Stage2_compute_one: zero or one list, 3' end first), S2X_ENDS
+        (Stage2_compute_ends after Stage2pairs_filter_unique_ends) or S2X_STARTS (Stage2_compute_starts after
+        Stage2pairs_filter_unique_starts: each list 3' end first)."""
         probs, qbuf, qucbuf = self.build_stage2x_batch(calls, kind)
         results, paths, pairs = self.stage2x_batch_raw(probs, qbuf, qucbuf)
         out = []

@@ -35,11 +35,13 @@
  *                            seeding above, then Diag_compute_bounds (diag.c:597),
  *                            align_compute_lookback (stage2.c:4402), convert_to_nucleotides (:5334)
  *                            and Stage2_filter_unique (:6013)
- *   gmapdp_stage2x_batch     Stage2_compute_one (stage2.c:6754) and Stage2_compute_ends (:7087) as stage 3
- *                            calls them on a query segment (stage3.c:11382 / 15849): the seeding with the
- *                            minor index, Diag_max_bounds (diag.c:894), align_compute_lookback without
- *                            skip_repetitive_p (ENDS: localp and middlep false), convert_to_nucleotides
- *                            with query_offset, ENDS: Stage2pairs_filter_unique_ends (:6218)
+ *   gmapdp_stage2x_batch     Stage2_compute_one (stage2.c:6754), Stage2_compute_ends (:7087) and
+ *                            Stage2_compute_starts (:6914) as stage 3 calls them on a query segment
+ *                            (stage3.c:11382 / 15849 / 15955): the seeding with the minor index,
+ *                            Diag_max_bounds (diag.c:894), align_compute_lookback without skip_repetitive_p
+ *                            (ENDS: localp and middlep false; STARTS: the same with
+ *                            align_compute_lookforward, :5062), convert_to_nucleotides with query_offset,
+ *                            ENDS / STARTS: Stage2pairs_filter_unique_ends / _starts (:6218 / :6114)
  *
  * Semantics: every result is bit-identical to the reference's nosimd build
  * (Dynprog_standard + Dynprog_traceback_std), or with GMAPDP_SIMD to its SIMD builds
@@ -742,7 +744,7 @@ int gmapdp_stage2_batch (gmapdp_ctx *ctx, const gmapdp_stage2_problem *problems,
                          size_t path_cap, gmapdp_path_pair *pairs, size_t pair_cap, size_t *paths_needed,
                          size_t *pairs_needed);
 
-/* The two stage-2 entry points stage 3 calls on a segment of the query, with stage 3's arguments
+/* The three stage-2 entry points stage 3 calls on a segment of the query, with stage 3's arguments
  * (oligoindices_minor: 8-mers, diag_lookback 60, suffnconsecutive 10; skip_repetitive_p false, favor_right_p
  * false, genestrand 0, genomealt == genome, use_canonical_middle_p false; Stage2_setup as for
  * gmapdp_stage2_problem):
@@ -755,7 +757,14 @@ int gmapdp_stage2_batch (gmapdp_ctx *ctx, const gmapdp_stage2_problem *problems,
  *                    and a query position where no hit scored above 0 restarts all its hits at score 8
  *                    (stage2.c:3955-3980).  Every traced path is converted without gap holders (5' end first) and
  *                    the lists go through Stage2pairs_filter_unique_ends (:6218).
- * Neither applies the coverage filter (they chain whenever totalpositions > 0), both take Diag_max_bounds
+ *   GMAPDP_S2X_STARTS Stage2_compute_starts (stage2.c:6914) as stage3.c:15955 / 16166 call it for an unaligned 5'
+ *                    end: ENDS' arguments with align_compute_lookforward (:5062).  The sweep runs from the last
+ *                    query position down and links every hit to one further 3'; a path is traced from its cell
+ *                    towards the 3' end, and MIN_TERMINAL_NCONSECUTIVE prunes its 5' end.  Every traced path
+ *                    is converted without gap holders and returned 3' end first (List_reverse(pairs), :7040);
+ *                    the lists go through Stage2pairs_filter_unique_starts (:6114: by the first pair's genomepos
+ *                    descending, then the last pair's descending).
+ * None applies the coverage filter (they chain whenever totalpositions > 0), all take Diag_max_bounds
  * (diag.c:894: every query position is active over the whole window, querystart 0, queryend querylength - 1)
  * and add query_offset to every pair's querypos.  The struct is gmapdp_stage2_problem followed by kind and
  * query_offset; flags must be 0 (cross-species scoring is not offered for these calls).  Domain as for
@@ -763,6 +772,7 @@ int gmapdp_stage2_batch (gmapdp_ctx *ctx, const gmapdp_stage2_problem *problems,
  * positions), genomic positions below 2^31, the context's mode STANDARD or stranded. */
 #define GMAPDP_S2X_ONE  1
 #define GMAPDP_S2X_ENDS 2
+#define GMAPDP_S2X_STARTS 3
 typedef struct {
   int32_t qoff;
   int32_t querylength;
@@ -774,15 +784,16 @@ typedef struct {
   int32_t splicingp;
   int32_t maxintronlen;
   int32_t flags;           /* must be 0 */
-  int32_t kind;            /* GMAPDP_S2X_ONE or GMAPDP_S2X_ENDS; one value per batch */
+  int32_t kind;            /* GMAPDP_S2X_ONE, _ENDS or _STARTS; one value per batch */
   int32_t query_offset;    /* added to every pair's querypos (convert_to_nucleotides) */
 } gmapdp_stage2x_problem;
 
 /* n calls of one kind, in gmapdp_stage2_batch's formats: per call the returned lists in the returned list's
- * order (ONE: nresults 0 or 1) as path records, each record's pairs in that list's order.  status is 0 (no
+ * order (ONE: nresults 0 or 1) as path records, each record's pairs in that list's order (ONE and STARTS: 3' end
+ * first).  status is 0 (no
  * positions) or 2 (chained), npaths the paths traced, diag_querystart / diag_queryend 0 / querylength - 1.
  * GMAPDP_ESPACE and *paths_needed / *pairs_needed as in gmapdp_stage2_batch.  GMAPDP_EINVAL (with a
- * message): a mix of kinds, a kind other than 1 or 2, flags != 0, querylength <= 8, a negative maxintronlen,
+ * message): a mix of kinds, a kind outside 1..3, flags != 0, querylength <= 8, a negative maxintronlen,
  * a context of a non-stranded cmet / atoi / ttoc mode (2, 4, 6).  GMAPDP_ENOGENOME without a genome. */
 int gmapdp_stage2x_batch (gmapdp_ctx *ctx, const gmapdp_stage2x_problem *problems, int n, const char *qseq,
                           const char *qseq_uc, size_t qbytes, gmapdp_stage2_result *results, gmapdp_path *paths,
