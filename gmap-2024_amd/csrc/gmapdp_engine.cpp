@@ -354,6 +354,7 @@ struct gmapdp_ctx {
   bool poll = false;              // GMAPDP_CTX_POLL_SYNC: ev_block is polled with sleeps in between
   bool long_queries = false;      // GMAPDP_CTX_LONG_QUERIES: the seeding's long class (oligo_classify)
   std::atomic<unsigned long long> long_calls{0};  // seeding problems classified long so far
+  std::atomic<unsigned long long> pool_regrows{0};  // extra attempts of s2_batch_core after a pool overflow
   DevBuf probs, order, qseq, qseq_uc, results, pairs, gdirs;
   DevBuf din, dout;    // run_batch: all inputs / all outputs of one synchronous batch
   HostBuf hin, hout;   // their pinned host images
@@ -3820,6 +3821,7 @@ static int s2_batch_core(gmapdp_ctx* ctx, int n, std::vector<gmapdp_oligo_proble
     if (attempt >= 8) return fail(ctx, GMAPDP_ENOMEM, "stage-2 output pools keep overflowing%s", hipSuccess);
     pcap = std::max<size_t>(2 * pcap, (size_t)cnt[1] + 16);
     qcap = std::max<size_t>(2 * qcap, (size_t)cnt[2] + 64);
+    ctx->pool_regrows.fetch_add(1, std::memory_order_relaxed);
   }
 }
 
@@ -4634,6 +4636,10 @@ int gmapdp_stage2_plan_seeding_classes(const gmapdp_stage2_plan* plan, int* n16,
 
 unsigned long long gmapdp_long_query_calls(const gmapdp_ctx* ctx) {
   return ctx ? ctx->long_calls.load(std::memory_order_relaxed) : 0ull;
+}
+
+unsigned long long gmapdp_stage2_pool_regrows(const gmapdp_ctx* ctx) {
+  return ctx ? ctx->pool_regrows.load(std::memory_order_relaxed) : 0ull;
 }
 
 void gmapdp_stage2_plan_destroy(gmapdp_stage2_plan* plan) { delete plan; }

@@ -2859,6 +2859,9 @@ __global__ __launch_bounds__(64) void s2c_kernel(
   pbase = __shfl(pbase, 0, 64);
   if (nres > 0 && pbase + nres > path_cap) {
     if (lane == 0) {
+      // (the reserved slots below the capacity become empty records: the pool's readers -- the fetch, pc_kernel --
+      // count them, and would else see uninitialised memory or an earlier run's lists)
+      for (unsigned long long k = pbase; k < path_cap; k++) paths_out[k] = gmapdp_path{0, 0, 0};
       R.status = kS2Overflow;
       results[P.index] = R;
     }
@@ -2922,6 +2925,8 @@ __global__ __launch_bounds__(64) void s2c_kernel(
     qb = __shfl(qb, 0, 64);
     if (qb + total > pair_cap) {
       if (lane == 0) {
+        // (the lists written so far stay; the call's other reserved path slots become empty records, as above)
+        for (int k = r; k < nres; k++) paths_out[pbase + k] = gmapdp_path{0, 0, 0};
         R.status = kS2Overflow;
         results[P.index] = R;
       }

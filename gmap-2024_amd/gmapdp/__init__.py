@@ -304,6 +304,7 @@ def load_library(path=LIB_PATH):
         "gmapdp_stage2_plan_seeding_classes": (C.c_int, [C.c_void_p, P(C.c_int), P(C.c_int)]),
         "gmapdp_stage2_plan_seeding_results": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "gmapdp_long_query_calls": (C.c_ulonglong, [C.c_void_p]),
+        "gmapdp_stage2_pool_regrows": (C.c_ulonglong, [C.c_void_p]),
         "gmapdp_stage2_plan_destroy": (None, [C.c_void_p]),
         "gmapdp_genome_prob_entries": (C.c_size_t, [C.c_void_p, C.c_int]),
         "gmapdp_genome_splice_sites": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -866,6 +867,11 @@ class Engine:
         """Seeding problems this context has put into the long class so far (CTX_LONG_QUERIES)."""
         return int(self.lib.gmapdp_long_query_calls(self.h))
 
+    def stage2_pool_regrows(self):
+        """Extra attempts stage2_batch / stage2x_batch made on this context so far after a device output pool
+        overflowed (gmapdp_stage2_pool_regrows)."""
+        return int(self.lib.gmapdp_stage2_pool_regrows(self.h))
+
     # -- batched Stage2_scan (seeding with the major index + Diag_update_coverage) ------------------
     @staticmethod
     def build_scan_batch(calls):
@@ -1026,7 +1032,7 @@ class Engine:
         return out
 
     def stage2_plan_raw(self, probs, qbuf, qucbuf, run_qbuf=None, run_qucbuf=None, compact_out=None,
-                        cross_species=False, whats=(3,), reruns=0):
+                        cross_species=False, whats=(3,), reruns=0, prior_runs=()):
         """The device-resident Stage2_compute plan (bench.py's path): gmapdp_stage2_plan_create on
         (probs, qbuf, qucbuf) -- its sizing run, the measured re-layout, the 16-bit seeding class --,
         gmapdp_stage2_plan_run(what = 3) against device copies of the query arenas (run_qbuf /
@@ -1036,7 +1042,8 @@ class Engine:
         (gmapdp_expand_path_pairs): compact_out["pairs"] (an arena like `pairs`), ["bytes"], ["bound"]
         (gmapdp_stage2_plan_compact_bound).  cross_species: the plan's calls carry GMAPDP_S2_CANONICAL_MIDDLE
         (probs is not modified).  whats: the `what` values of the run, in order ((3,) or (1, 4, 8, 16));
-        reruns: how many more times the same run is made before the fetch."""
+        reruns: how many more times the same run is made before the fetch; prior_runs: (qbuf, qucbuf) arenas of the
+        same layout that the plan is run on, in order, before that (their outputs are not fetched)."""
         lib, n = self.lib, len(probs)
         if cross_species:
             probs = probs.copy()
@@ -1064,6 +1071,12 @@ class Engine:
             assert len(rq) == len(qbuf) and len(rqu) == len(qucbuf)
             d_q, d_quc = dbuf(len(rq), rq), dbuf(len(rqu), rqu)
             d_res = dbuf(n * STAGE2_RESULT_DTYPE.itemsize)
+            for pq, pqu in prior_runs:
+                assert len(pq) == len(qbuf) and len(pqu) == len(qucbuf)
+                d_pq, d_pquc = dbuf(len(pq), pq), dbuf(len(pqu), pqu)
+                for what in whats:
+                    self._check(lib.gmapdp_stage2_plan_run(self.h, plan, d_pq, d_pquc, d_res, what, None),
+                                "gmapdp_stage2_plan_run")
             for _ in range(1 + reruns):
                 for what in whats:
                     self._check(lib.gmapdp_stage2_plan_run(self.h, plan, d_q, d_quc, d_res, what, None),

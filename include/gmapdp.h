@@ -821,7 +821,17 @@ int gmapdp_stage2x_batch (gmapdp_ctx *ctx, const gmapdp_stage2x_problem *problem
  * runs beside a DP plan's launches (tested); two runs of the same plan must be ordered.  DP plans: see
  * gmapdp_plan_run_launch.
  * Creating a plan of any kind sizes the context's grow-only buffers and runs on the context's stream:
- * create plans while no run is in flight on the context. */
+ * create plans while no run is in flight on the context.
+ * The pools are fixed when the plan is made (16 + 4 n path records, 64 + 3 * the sum of the query lengths pair
+ * records) and never grow.  A call that does not fit reserves its slots all the same, in the order the waves
+ * finish, and reports status -2: its result's other fields are not to be used.  Of its path slots, those below
+ * the pool's capacity hold either a list it wrote before its pair reservation failed (a valid record, its pairs
+ * in the pool, owned by no call a caller should read) or an empty record (pair_offset 0, npairs 0); none holds
+ * uninitialised memory or an earlier run's record.  Its reserved pair slots are not written.  The counters
+ * count past the capacities; gmapdp_stage2_plan_fetch clamps them, gmapdp_stage2_plan_compact_pairs takes a
+ * count above the path pool's size as that size.  The lists of all path records within the pool are disjoint
+ * and lie within the pair pool, so the compact stream keeps to gmapdp_stage2_plan_compact_bound whatever
+ * overflowed. */
 typedef struct gmapdp_stage2_plan gmapdp_stage2_plan;
 int gmapdp_stage2_plan_create (gmapdp_ctx *ctx, const gmapdp_stage2_problem *problems, int n, const char *qseq,
                                const char *qseq_uc, size_t qbytes, gmapdp_stage2_plan **plan);
@@ -847,6 +857,10 @@ int gmapdp_stage2_plan_seeding_classes (const gmapdp_stage2_plan *plan, int *n16
 /* Seeding problems the context has put into the long class so far, over all its stage-2 entry points
  * (0 for ever without GMAPDP_CTX_LONG_QUERIES). */
 unsigned long long gmapdp_long_query_calls (const gmapdp_ctx *ctx);
+/* How many times gmapdp_stage2_batch and gmapdp_stage2x_batch on this context have grown their device output
+ * pools and run the chaining kernels again because a call reported an overflow (first guesses: 16 + 2 n path
+ * records, 64 + 2 * the sum of the query lengths pair records; one count per extra attempt). */
+unsigned long long gmapdp_stage2_pool_regrows (const gmapdp_ctx *ctx);
 /* The compact stream of a finished chaining run's path pairs (gmapdp_plan_compact_pairs' format, 21-B RAW
  * ops: gmapdp_path_pair records with a jump or a negative position): one list per record of the plan's path
  * pool (*path_cap of them; records past the pool's count are empty lists).  d_offsets: path_cap + 1 uint64
