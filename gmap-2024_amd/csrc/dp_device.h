@@ -98,6 +98,19 @@ __device__ __forceinline__ char decode_nt(const uint32_t* __restrict__ blocks, u
   const uint32_t x = (w >> (2u * (bit & 15u))) & 3u;
   return (char)((0x54474341u >> (8u * x)) & 0xffu);  // "ACGT"
 }
+// The alternate allele at pos (gmap --use-snps; uncompress_mmap_snps_subst, genome.c:9419, and Genome_get_char,
+// :11004): the character comes from the alternate genome's high / low word, 'N' goes where the *primary*
+// genome's flag bit is set, and the alternate genome's own flag word is never read.
+__device__ __forceinline__ char decode_nt_alt(const uint32_t* __restrict__ blocks,
+                                              const uint32_t* __restrict__ ablocks, uint64_t nwords, uint64_t pos) {
+  const uint64_t ptr = (pos >> 5) * 3u;
+  if (ptr + 2 >= nwords) return 'N';  // beyond the allocation: as decode_nt
+  const uint32_t bit = pos & 31u;
+  if ((blocks[ptr + 2] >> bit) & 1u) return 'N';
+  const uint32_t w = (bit < 16) ? ablocks[ptr + 1] : ablocks[ptr];
+  const uint32_t x = (w >> (2u * (bit & 15u))) & 3u;
+  return (char)((0x54474341u >> (8u * x)) & 0xffu);  // "ACGT"
+}
 __device__ __forceinline__ char compl_nt(char c) {
   // only A C G T N * occur: complement of ACGT via a 4-entry table, N and * unchanged
   return (c == 'A') ? 'T' : (c == 'C') ? 'G' : (c == 'G') ? 'C' : (c == 'T') ? 'A' : c;
@@ -112,6 +125,16 @@ __device__ __forceinline__ char genomic_nt(const uint32_t* __restrict__ blocks, 
   const uint64_t pos = watson ? chroffset + g : chrhigh - g;
   if (pos < chroffset || pos >= chrhigh) return '*';
   const char c = decode_nt(blocks, nwords, pos);
+  return watson ? c : compl_nt(c);
+}
+// its alternate allele (get_genomic_nt's *g_alt): the same bounds and complement
+__device__ __forceinline__ char genomic_nt_alt(const uint32_t* __restrict__ blocks,
+                                               const uint32_t* __restrict__ ablocks, uint64_t nwords, int genomicpos,
+                                               uint64_t chroffset, uint64_t chrhigh, bool watson) {
+  const uint64_t g = (uint64_t)(int64_t)genomicpos;
+  const uint64_t pos = watson ? chroffset + g : chrhigh - g;
+  if (pos < chroffset || pos >= chrhigh) return '*';
+  const char c = decode_nt_alt(blocks, ablocks, nwords, pos);
   return watson ? c : compl_nt(c);
 }
 // Character i of Genome_get_segment_right(left=pos, L, chrhigh=bound) or
@@ -135,13 +158,34 @@ __device__ __forceinline__ char segment_nt(const uint32_t* __restrict__ blocks, 
   }
   return revcomp ? compl_nt(c) : c;
 }
+// The same character of the alternate segment (segmentalt): '*' at the same positions, the same complement.
+// (A twin of segment_nt rather than one template over the decoder: the kernels without an alternate allele
+// keep the function they were compiled from.)
+__device__ __forceinline__ char segment_nt_alt(const uint32_t* __restrict__ blocks,
+                                               const uint32_t* __restrict__ ablocks, uint64_t nwords, uint32_t i,
+                                               uint32_t L, uint64_t pos, uint64_t bound, bool leftvariant,
+                                               bool revcomp) {
+  const uint64_t j = revcomp ? L - 1u - i : i;
+  char c;
+  if (!leftvariant) {
+    if (pos >= bound) return '*';
+    if (pos + L >= bound && j + (pos + L - bound) >= L) return '*';
+    c = decode_nt_alt(blocks, ablocks, nwords, pos + j);
+  } else {
+    if (pos < bound) return '*';
+    if (pos < bound + L && j < bound + L - pos) return '*';
+    c = decode_nt_alt(blocks, ablocks, nwords, pos - L + j);
+  }
+  return revcomp ? compl_nt(c) : c;
+}
 
 // ---- LDS carve (must match lds_bytes_dp on the host) ----
 __host__ __device__ constexpr size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
 struct Carve {
   size_t sc, q, quc, gch, gcls, dirs, total;
+  size_t gcha, gclsa;  // the alternate allele's characters and classes (carve_dp with alt only)
 };
-__host__ __device__ inline Carve carve_dp(int rlength, int glength, int R, bool dirs_lds) {
+__host__ __device__ inline Carve carve_dp(int rlength, int glength, int R, bool dirs_lds, bool alt = false) {
   Carve cv;
   size_t off = 0;
   const size_t srow = (size_t)(rlength + 2);
@@ -150,6 +194,11 @@ __host__ __device__ inline Carve carve_dp(int rlength, int glength, int R, bool 
   cv.quc = off;  off = align16(off + (size_t)(rlength + 1));
   cv.gch = off;  off = align16(off + (size_t)(glength + 1));
   cv.gcls = off; off = align16(off + (size_t)(glength + 1));
+  cv.gcha = cv.gclsa = 0;
+  if (alt) {
+    cv.gcha = off;  off = align16(off + (size_t)(glength + 1));
+    cv.gclsa = off; off = align16(off + (size_t)(glength + 1));
+  }
   cv.dirs = off;
   if (dirs_lds) off = align16(off + (size_t)(glength + 1) * 4u * (size_t)R * 8u);
   cv.total = off;
@@ -203,28 +252,52 @@ struct GClassView {  // genome character of column c from its class (A C G T N *
   __device__ char operator[](int c) const { return (char)((0x2A4E54474341ull >> (8u * cls[c])) & 0xffu); }
 };
 
-// Diagonal run: cells (r-j, c-j), j in [0, n)  (dynprog.c:1861-1915, traceback_nogaps)
-template <typename QV, typename GV>
+// The alternate allele as the emitters see it (gmap --use-snps).  NoAlt: the genome has none, every record's
+// genomealt is its genome character, and the emitters compile to what they were without one.  AltView: the
+// staged alternate segment by DP column and the alternate genome's blocks (genome skips re-read characters).
+struct NoAlt {};
+struct AltView {
+  const char* gch;
+  const uint32_t* blocks;
+};
+
+// Diagonal run: cells (r-j, c-j), j in [0, n)  (dynprog.c:1861-1915, traceback_nogaps).  With an alternate
+// allele the test is three-way on (c2, c2_alt): a match through either, else ambiguous when the consistency
+// table holds for either (Dynprog_consistent_p, dynprog.c:895), else a mismatch; the '*' test reads c2 alone.
+template <typename QV, typename GV, typename ALT = NoAlt>
 __device__ __forceinline__ void emit_diag(int lane, int r, int c, int n, const Geo& G, const QV& q, const QV& quc,
                                           const GV& gch, const uint8_t* __restrict__ cons, gmapdp_pair* out,
-                                          Tally& t) {
+                                          Tally& t, ALT alt = ALT()) {
+  constexpr bool kAlt = !__is_same(ALT, NoAlt);
   for (int base = 0; base < n; base += 64) {
     const int j = base + lane;
     const bool active = j < n;
     bool notstar = false, good = false, matchish = false, amb = false;
     int qp = 0, gp = 0;
     char c1 = 0, c2 = 0;
+    [[maybe_unused]] char c2a = 0;
     if (active) {
       const int rr = r - j, cc = c - j;
       c1 = q[rr];
       const char c1u = quc[rr];
       c2 = gch[cc];
       notstar = c2 != '*';
-      if (c1u == c2) {
-        matchish = true;
-      } else if (cons[(uint8_t)(c1u & 127) * kNClass + gclass(c2)]) {
-        matchish = true;
-        amb = true;
+      if constexpr (kAlt) {
+        c2a = alt.gch[cc];
+        if (c1u == c2 || c1u == c2a) {
+          matchish = true;
+        } else if (cons[(uint8_t)(c1u & 127) * kNClass + gclass(c2)] ||
+                   cons[(uint8_t)(c1u & 127) * kNClass + gclass(c2a)]) {
+          matchish = true;
+          amb = true;
+        }
+      } else {
+        if (c1u == c2) {
+          matchish = true;
+        } else if (cons[(uint8_t)(c1u & 127) * kNClass + gclass(c2)]) {
+          matchish = true;
+          amb = true;
+        }
       }
       qp = G.qpos(rr);
       gp = G.gpos(cc);
@@ -234,7 +307,10 @@ __device__ __forceinline__ void emit_diag(int lane, int r, int c, int n, const G
     t.nmatches += __popcll(ballot(active && notstar && matchish));
     t.nmismatches += __popcll(ballot(active && notstar && !matchish));
     if (good) {
-      put_pair(out, t.count + lanes_below(mgood, lane), qp, gp, 0, c1, matchish ? (amb ? ':' : '*') : ' ', c2, c2);
+      if constexpr (kAlt)
+        put_pair(out, t.count + lanes_below(mgood, lane), qp, gp, 0, c1, matchish ? (amb ? ':' : '*') : ' ', c2, c2a);
+      else
+        put_pair(out, t.count + lanes_below(mgood, lane), qp, gp, 0, c1, matchish ? (amb ? ':' : '*') : ' ', c2, c2);
     }
     t.count += __popcll(mgood);
     if (mgood) t.seen = true;
@@ -264,10 +340,13 @@ __device__ __forceinline__ void emit_queryskip(int lane, int rs, int c, int dist
 }
 
 // Genome skip: Pairpool_add_genomeskip(&add_dashes_p, pairs, r, cs, dist, NULL, ...) (pairpool.c:1068):
-// columns cs, cs-1, ...; dist >= 9 gives one gap holder
+// columns cs, cs-1, ...; dist >= 9 gives one gap holder.  With an alternate allele each record carries
+// get_genomic_nt's *g_alt (pairpool.c:1158).
+template <typename ALT = NoAlt>
 __device__ __forceinline__ void emit_genomeskip(int lane, int r, int cs, int dist, const Geo& G, bool watson,
                                                 uint64_t chroffset, uint64_t chrhigh, const uint32_t* blocks,
-                                                uint64_t nwords, gmapdp_pair* out, Tally& t) {
+                                                uint64_t nwords, gmapdp_pair* out, Tally& t,
+                                                ALT alt = ALT()) {
   if (dist >= kMicrointronLength) {
     if (lane == 0) put_pair(out, t.count, -1, -1, dist, ' ', ' ', ' ', ' ');
     t.count += 1;
@@ -283,7 +362,11 @@ __device__ __forceinline__ void emit_genomeskip(int lane, int r, int cs, int dis
     const uint64_t mgood = ballot(good);
     if (good) {
       const char c2 = genomic_nt(blocks, nwords, gp, chroffset, chrhigh, watson);
-      put_pair(out, t.count + lanes_below(mgood, lane), qp, gp, 0, ' ', '-', c2, c2);
+      if constexpr (!__is_same(ALT, NoAlt))
+        put_pair(out, t.count + lanes_below(mgood, lane), qp, gp, 0, ' ', '-', c2,
+                 genomic_nt_alt(blocks, alt.blocks, nwords, gp, chroffset, chrhigh, watson));
+      else
+        put_pair(out, t.count + lanes_below(mgood, lane), qp, gp, 0, ' ', '-', c2, c2);
     }
     const int nw = __popcll(mgood);
     t.count += nw;
@@ -372,11 +455,17 @@ struct PackedDirs {
 
 // NB (whole-wave fills only): the band is narrower than the wave's 64 R elements, so the last lane's last
 // element is never a valid cell and the E / H values shifted into it need no -infinity default.
-template <int R, bool CARRY, int S = 64, bool PK = (S < 64), bool STORE = false, bool DPK = false, bool NB = false>
+// ALT (gmap --use-snps, Dynprog_standard dynprog.c:1528-1531): a column carries a second wave-uniform class,
+// gcla[c], and a cell scores max(sc[gi][row], sc[gia][row]).  Where the two classes agree -- nearly every
+// column -- the wave takes a scalar branch around the second read, so such a column costs one more class read.
+template <int R, bool CARRY, int S = 64, bool PK = (S < 64), bool STORE = false, bool DPK = false, bool NB = false,
+          bool ALT = false>
 __device__ __forceinline__ void fill_band(int lane, int rlen, int glen, int lband, int uband, int open, int ext,
                                           int late, int track, const int8_t* sc, int srow, const uint8_t* gcl,
                                           uint64_t* dirs, const BridgeCarry* bc_, int& bestr, int& bestc,
-                                          int gmax = 0, int* smat = nullptr, int* best_score = nullptr) {
+                                          int gmax = 0, int* smat = nullptr, int* best_score = nullptr,
+                                          const uint8_t* gcla = nullptr) {
+  static_assert(!ALT || (S == 64 && !PK && !CARRY), "alternate allele: whole-wave single / end fills");
   static_assert(S == 64 || (R == 1 && !CARRY), "segmented fills are single-word, no bridge carry");
   static_assert(!STORE || S == 64, "score matrices are stored by whole-wave fills only");
   static_assert(!DPK || (R == 1 && S == 64), "packed direction words: one-word bands");
@@ -444,6 +533,8 @@ __device__ __forceinline__ void fill_band(int lane, int rlen, int glen, int lban
     const int row0 = (c <= uband) ? oce : kNegInf32;  // row 0 of this column (dynprog.c:1318-1325)
     const int8_t* scg = PK ? sc : sc + gi * srow;
     const int gi4 = gi << 2;  // packed: bit offset of the class in the row's score word
+    [[maybe_unused]] int gia = gi;
+    if constexpr (ALT) gia = __builtin_amdgcn_readfirstlane(gcla[c]);
 
     int Ein[R], Hin[R];
 #pragma unroll
@@ -471,6 +562,9 @@ __device__ __forceinline__ void fill_band(int lane, int rlen, int glen, int lban
         s = __builtin_amdgcn_sbfe(*(const __attribute__((address_space(3))) int32_t*)(size_t)(scb + 4u * (uint32_t)rr),
                                   gi4, 4);
       else s = __builtin_amdgcn_sbfe(reinterpret_cast<const int32_t*>(sc)[rr], gi4, 4);
+      if constexpr (ALT) {
+        if (gia != gi) s = max(s, (int)(sc + gia * srow)[rr]);  // (wave-uniform: a scalar branch)
+      }
       // Egap (dynprog.c:1518-1524)
       const int es = Hin[i] + open;
       eb[i] = Ein[i] > es - late;
@@ -794,12 +888,12 @@ struct RowDirs {
 // t (0 nogap=HORIZ, 1 nogap=VERT, 2 Egap=HORIZ, 3 Fgap=VERT) of cell (r, c), 0 (DIAG) for
 // cells the fill did not write.  Dynprog_traceback_8/_16 (dynprog_simd.c:9154/9553) walk the
 // same way, so the SIMD-semantics kernel shares this with its own direction layout.
-template <typename DA, typename QV, typename GV>
+template <typename DA, typename QV, typename GV, typename ALT = NoAlt>
 __device__ __forceinline__ void traceback_walk(int lane, const DA& dir, int r, int c, const Geo& G, const QV& q,
                                                const QV& quc, const GV& gch, const uint8_t* __restrict__ cons,
                                                bool watson, uint64_t chroffset, uint64_t chrhigh,
                                                const uint32_t* __restrict__ blocks, uint64_t nwords,
-                                               gmapdp_pair* out, Tally& t, int mode = 0) {
+                                               gmapdp_pair* out, Tally& t, int mode = 0, ALT alt = ALT()) {
   while (r > 0 && c > 0) {
     const uint32_t isV = dir(c, 1, r);
     const uint32_t isH = dir(c, 0, r);
@@ -814,7 +908,7 @@ __device__ __forceinline__ void traceback_walk(int lane, const DA& dir, int r, i
       }
       const int dist = n + 1;
       const int c_end = (c - n - 1) > 0 ? (c - n - 1) : 0;
-      emit_genomeskip(lane, r, c_end + dist, dist, G, watson, chroffset, chrhigh, blocks, nwords, out, t);
+      emit_genomeskip(lane, r, c_end + dist, dist, G, watson, chroffset, chrhigh, blocks, nwords, out, t, alt);
       c = c_end;
     } else if (isV) {
       // F chain up column c: rows r, r-1, ... while Fgap == VERT
@@ -839,7 +933,7 @@ __device__ __forceinline__ void traceback_walk(int lane, const DA& dir, int r, i
         const uint64_t stop = ~ballot(cont && inrange);
         if (stop) { n = base + __ffsll((long long)stop) - 1; break; }
       }
-      emit_diag(lane, r, c, n, G, q, quc, gch, cons, out, t);
+      emit_diag(lane, r, c, n, G, q, quc, gch, cons, out, t, alt);
       r -= n;
       c -= n;
     }
@@ -850,7 +944,7 @@ __device__ __forceinline__ void traceback_walk(int lane, const DA& dir, int r, i
   } else if (mode == 2 || (mode == 0 && c == 0)) {
     emit_queryskip(lane, r, 1, r, G, q, out, t);  // LAZY_INDEL
   } else {
-    emit_genomeskip(lane, 1, c, c, G, watson, chroffset, chrhigh, blocks, nwords, out, t);
+    emit_genomeskip(lane, 1, c, c, G, watson, chroffset, chrhigh, blocks, nwords, out, t, alt);
   }
 }
 
@@ -867,14 +961,16 @@ struct BandDirs {
   }
 };
 
-template <int R, typename WORD = uint64_t, typename QV = const char*, typename GV = const char*>
+template <int R, typename WORD = uint64_t, typename QV = const char*, typename GV = const char*,
+          typename ALT = NoAlt>
 __device__ __forceinline__ void traceback_band(int lane, const WORD* dirs, int W, int uband, int r, int c,
                                                const Geo& G, const QV& q, const QV& quc, const GV& gch,
                                                const uint8_t* __restrict__ cons, bool watson, uint64_t chroffset,
                                                uint64_t chrhigh, const uint32_t* __restrict__ blocks,
-                                               uint64_t nwords, gmapdp_pair* out, Tally& t, int bitoff = 0) {
+                                               uint64_t nwords, gmapdp_pair* out, Tally& t, int bitoff = 0,
+                                               ALT alt = ALT()) {
   const BandDirs<R, WORD> d{dirs, W, uband, bitoff};
-  traceback_walk(lane, d, r, c, G, q, quc, gch, cons, watson, chroffset, chrhigh, blocks, nwords, out, t);
+  traceback_walk(lane, d, r, c, G, q, quc, gch, cons, watson, chroffset, chrhigh, blocks, nwords, out, t, 0, alt);
 }
 
 // ---- row-held fill of the genome-gap kernel: a lane keeps one query row for a stretch of T columns ----

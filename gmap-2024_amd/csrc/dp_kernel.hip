@@ -36,6 +36,8 @@
 //    .genomecomp blocks (3 x u32 per 32 nt).
 #include "dp_device.h"
 
+#include <type_traits>
+
 namespace gmapdp {
 
 // Phase timing of gg_kernel (tools_oi_timing.py gg; GMAPDP_OI_TIMING variant of the library only):
@@ -70,14 +72,19 @@ extern "C" int gmapdp_debug_gg_marks(unsigned long long* out) {
 
 // ROWS: lanes over query rows (fill_rows, R = row words) instead of band offsets, for bands much
 // wider than the query; dpr_kernel below.
-template <int R, bool DIRS_LDS, bool ROWS>
+// ALT: the context has an alternate-allele genome bound (gmap --use-snps; dpa_kernel below, band layout
+// only).  The alternate segment is staged beside the reference one (characters and classes), the fill
+// scores a column by both classes and the emitters apply the three-way test and write c2_alt.
+template <int R, bool DIRS_LDS, bool ROWS, bool ALT = false>
 __device__ __forceinline__ void dp_body(
     const DevProblem* __restrict__ probs, const int* __restrict__ order,
     const uint32_t* __restrict__ blocks, uint64_t nwords,
     const char* __restrict__ qseq, const char* __restrict__ qseq_uc,
     const int8_t* __restrict__ sctab, const uint8_t* __restrict__ constab,
     gmapdp_result* __restrict__ results, gmapdp_pair* __restrict__ pairs,
-    uint64_t* __restrict__ gdirs) {
+    uint64_t* __restrict__ gdirs, const uint32_t* __restrict__ ablocks = nullptr) {
+  static_assert(!ALT || !ROWS, "alternate allele: band layout only");
+  using AltT = typename std::conditional<ALT, AltView, NoAlt>::type;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x;
   const int pid = order[blockIdx.x];
@@ -88,12 +95,16 @@ __device__ __forceinline__ void dp_body(
   const int late = (flags & kFLate) ? 1 : 0;
   const bool rev = flags & kFRev;
   const int kind = P.kind;
-  const Carve cv = carve_dp(rlen, glen, R, DIRS_LDS);
+  const Carve cv = carve_dp(rlen, glen, R, DIRS_LDS, ALT);
   int8_t* sc = reinterpret_cast<int8_t*>(smem + cv.sc);
   char* q = reinterpret_cast<char*>(smem + cv.q);
   char* quc = reinterpret_cast<char*>(smem + cv.quc);
   char* gch = reinterpret_cast<char*>(smem + cv.gch);
   uint8_t* gcl = reinterpret_cast<uint8_t*>(smem + cv.gcls);
+  [[maybe_unused]] char* gcha = reinterpret_cast<char*>(smem + cv.gcha);
+  [[maybe_unused]] uint8_t* gcla = reinterpret_cast<uint8_t*>(smem + cv.gclsa);
+  AltT alt{};
+  if constexpr (ALT) alt = AltView{gcha, ablocks};
   uint64_t* dirs = DIRS_LDS ? reinterpret_cast<uint64_t*>(smem + cv.dirs)
                             : reinterpret_cast<uint64_t*>(reinterpret_cast<unsigned char*>(gdirs) + P.dirs_offset);
   const int8_t* sct = sctab + (size_t)P.mismatchtype * 128 * kNClass;
@@ -124,6 +135,12 @@ __device__ __forceinline__ void dp_body(
     const int c = rev ? glen - i : i + 1;  // end5 walks the segment from its right end
     gch[c] = c2;
     gcl[c] = gclass(c2);
+    if constexpr (ALT) {
+      const char c2a = segment_nt_alt(blocks, ablocks, nwords, (uint32_t)i, (uint32_t)glen, P.segpos, P.segbound,
+                                      segleft, segrc);
+      gcha[c] = c2a;
+      gcla[c] = gclass(c2a);
+    }
   }
   __syncthreads();
 
@@ -141,12 +158,16 @@ __device__ __forceinline__ void dp_body(
       if (r <= rlen) {
         const char c1u = quc[r], c2 = gch[r];
         mism = (c2 != '*') && (c1u != c2) && !cons[(uint8_t)(c1u & 127) * kNClass + gclass(c2)];
+        if constexpr (ALT) {  // (dynprog_single.c:376 / :390: a match or consistent through either allele)
+          const char c2a = gcha[r];
+          mism = mism && (c1u != c2a) && !cons[(uint8_t)(c1u & 127) * kNClass + gclass(c2a)];
+        }
       }
       nmism += __popcll(ballot(mism));
     }
     if (nmism <= 1) {
       // pushes r = 1..rlength without List_reverse: list order is r = rlength .. 1, a diagonal run
-      emit_diag(lane, rlen, rlen, rlen, G, q, quc, gch, cons, out, t);
+      emit_diag(lane, rlen, rlen, rlen, G, q, quc, gch, cons, out, t, alt);
       if (lane == 0) {
         gmapdp_result res;
         res.npairs = t.count;
@@ -171,6 +192,10 @@ __device__ __forceinline__ void dp_body(
     const int track = !is_end ? 0 : ((endalign == kQueryendIndels) ? 2 : 1);
     if constexpr (ROWS)
       fill_rows<R>(lane, rlen, glen, lband, uband, P.open, P.extend, late, track, sc, srow, gcl, dirs, bestr, bestc);
+    else if constexpr (ALT)
+      fill_band<R, false, 64, false, false, false, false, true>(lane, rlen, glen, lband, uband, P.open, P.extend, late,
+                                                                track, sc, srow, gcl, dirs, nullptr, bestr, bestc, 0,
+                                                                nullptr, nullptr, gcla);
     else
       fill_band<R, false>(lane, rlen, glen, lband, uband, P.open, P.extend, late, track, sc, srow, gcl, dirs,
                           nullptr, bestr, bestc);
@@ -182,14 +207,14 @@ __device__ __forceinline__ void dp_body(
 
   const bool skip = is_end && endalign != kQueryendNogaps && (flags & kFRequirePos);
   if (is_end && endalign == kQueryendNogaps) {
-    emit_diag(lane, bestr, bestc, bestr, G, q, quc, gch, cons, out, t);  // traceback_nogaps
+    emit_diag(lane, bestr, bestc, bestr, G, q, quc, gch, cons, out, t, alt);  // traceback_nogaps
   } else if (!skip) {
     if constexpr (ROWS)
       traceback_walk(lane, RowDirs<R>{dirs, W, uband}, bestr, bestc, G, q, quc, gch, cons, watson, P.chroffset,
                      P.chrhigh, blocks, nwords, out, t);
     else
       traceback_band<R>(lane, dirs, W, uband, bestr, bestc, G, q, quc, gch, cons, watson, P.chroffset, P.chrhigh,
-                        blocks, nwords, out, t);
+                        blocks, nwords, out, t, 0, alt);
   }
 
   int score = t.score + t.nmatches * kMatch + t.nmismatches * kMismatch;
@@ -231,6 +256,12 @@ __global__ __launch_bounds__(64) void dp_kernel(GMAPDP_DP_ARGS) {
 template <int R, bool DIRS_LDS>
 __global__ __launch_bounds__(64) void dpr_kernel(GMAPDP_DP_ARGS) {
   dp_body<R, DIRS_LDS, true>(probs, order, blocks, nwords, qseq, qseq_uc, sctab, constab, results, pairs, gdirs);
+}
+// dpa_kernel: dp_kernel under an alternate-allele genome (ablocks: its packed blocks, as long as `blocks`)
+template <int R, bool DIRS_LDS>
+__global__ __launch_bounds__(64) void dpa_kernel(GMAPDP_DP_ARGS, const uint32_t* __restrict__ ablocks) {
+  dp_body<R, DIRS_LDS, false, true>(probs, order, blocks, nwords, qseq, qseq_uc, sctab, constab, results, pairs,
+                                    gdirs, ablocks);
 }
 #undef GMAPDP_DP_ARGS
 
@@ -1144,15 +1175,44 @@ static void* kptr() {
   else return reinterpret_cast<void*>(&dp_kernel<R, D>);
 }
 
-size_t lds_bytes_dp(int rlength, int glength, int R, bool dirs_lds) {
-  return carve_dp(rlength, glength, R, dirs_lds).total;
+template <int R, bool D>
+static void* aptr() { return reinterpret_cast<void*>(&dpa_kernel<R, D>); }
+
+size_t lds_bytes_dp(int rlength, int glength, int R, bool dirs_lds, bool alt) {
+  return carve_dp(rlength, glength, R, dirs_lds, alt).total;
 }
 
+// ablocks: the context's alternate-allele genome, NULL without one (dpa_kernel instead of dp_kernel; no rows layout)
 hipError_t launch_dp(int R, bool dirs_lds, bool rows, int nblocks, size_t lds, hipStream_t stream,
                      const DevProblem* probs, const int* order, const uint32_t* blocks, uint64_t nwords,
                      const char* qseq, const char* qseq_uc, const int8_t* sctab, const uint8_t* constab,
-                     gmapdp_result* results, gmapdp_pair* pairs, uint64_t* gdirs) {
+                     gmapdp_result* results, gmapdp_pair* pairs, uint64_t* gdirs, const uint32_t* ablocks) {
   void* fn = nullptr;
+  if (ablocks) {
+    if (rows) return hipErrorInvalidValue;
+#define GMAPDP_ACASE(RR)                                 \
+  case RR:                                               \
+    fn = dirs_lds ? aptr<RR, true>() : aptr<RR, false>(); \
+    break;
+    switch (R) {
+      GMAPDP_ACASE(1)
+      GMAPDP_ACASE(2)
+      GMAPDP_ACASE(4)
+      GMAPDP_ACASE(8)
+      GMAPDP_ACASE(16)
+      GMAPDP_ACASE(32)
+      GMAPDP_ACASE(64)
+      default: return hipErrorInvalidValue;
+    }
+#undef GMAPDP_ACASE
+    if (lds > 64 * 1024) {
+      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+    }
+    void* args[] = {(void*)&probs, (void*)&order, (void*)&blocks, (void*)&nwords, (void*)&qseq, (void*)&qseq_uc,
+                    (void*)&sctab, (void*)&constab, (void*)&results, (void*)&pairs, (void*)&gdirs, (void*)&ablocks};
+    return hipLaunchKernel(fn, dim3(nblocks), dim3(64), args, lds, stream);
+  }
 #define GMAPDP_CASE(RR)                                          \
   case RR:                                                       \
     fn = dirs_lds ? kptr<RR, true, false>() : kptr<RR, false, false>();        \

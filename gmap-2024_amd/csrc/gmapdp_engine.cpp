@@ -38,11 +38,11 @@
 #include "../../include/gmapdp.h"
 
 namespace gmapdp {
-size_t lds_bytes_dp(int rlength, int glength, int R, bool dirs_lds);
+size_t lds_bytes_dp(int rlength, int glength, int R, bool dirs_lds, bool alt);
 hipError_t launch_dp(int R, bool dirs_lds, bool rows, int nblocks, size_t lds, hipStream_t stream,
                      const DevProblem* probs, const int* order, const uint32_t* blocks, uint64_t nwords,
                      const char* qseq, const char* qseq_uc, const int8_t* sctab, const uint8_t* constab,
-                     gmapdp_result* results, gmapdp_pair* pairs, uint64_t* gdirs);
+                     gmapdp_result* results, gmapdp_pair* pairs, uint64_t* gdirs, const uint32_t* ablocks);
 size_t lds_slot_dpx(int rlength, int glength);
 size_t lds_dirs_dpx(int gmax);
 size_t lds_slot_sx(int rlength, int glength, int B);
@@ -348,7 +348,9 @@ struct gmapdp_ctx {
   DevMem<uint32_t> d_genome;  // its own upload, or a view of a gmapdp_dgenome's / another context's
   uint64_t genome_words = 0;
   uint64_t genome_length = 0;
-  bool one_stream = false;   // GMAPDP_CTX_ONE_STREAM: no side streams (callers that run many contexts)
+  // the alternate-allele genome (gmap --use-snps' genomealt): as long as d_genome, dropped with it; NULL: none
+  DevMem<uint32_t> d_genome_alt;
+  bool one_stream = false;  // GMAPDP_CTX_ONE_STREAM: no side streams (callers that run many contexts)
   int plan_sides = kAux;     // side streams a plan's LPT spreads over (GMAPDP_CTX_TWO_SIDES: 2)
   hipEvent_t ev_block = nullptr;  // GMAPDP_CTX_BLOCKING_SYNC / _POLL_SYNC: batch completion waited on without spinning
   bool poll = false;              // GMAPDP_CTX_POLL_SYNC: ev_block is polled with sleeps in between
@@ -496,7 +498,8 @@ struct PlanCore {
   // kDpx: 64/S narrow problems per wave, R = S; kSx: SIMD-build single gaps, 64/B problems per wave,
   // R = B; kUxe / kUxg: SIMD-build end / genome gaps (triangle fills), one wave per problem, R = B
   // kDpRows: dp_kernel's recurrence with lanes over query rows (dpr_kernel), R = row words
-  enum Kind { kDp = 0, kGenomeGap = 1, kDpx = 2, kSx = 3, kUxe = 4, kUxg = 5, kDpRows = 7 };
+  // kDpAlt: dp_kernel under an alternate-allele genome (dpa_kernel), R = band words per lane
+  enum Kind { kDp = 0, kGenomeGap = 1, kDpx = 2, kSx = 3, kUxe = 4, kUxg = 5, kDpRows = 7, kDpAlt = 8 };
   struct Launch {
     int kind;
     int R;           // band words per lane (kDp, kGenomeGap) or segment width S (kDpx)
@@ -514,6 +517,7 @@ struct PlanCore {
   std::vector<int> gorder;           // gdev slots grouped by launch
   size_t pair_capacity = 0;
   size_t gdirs_bytes = 0;            // global scratch (spilled direction planes / bridge matrices)
+  bool alt = false;                  // classified under an alternate-allele genome (kDpAlt classes only)
 };
 
 static int fail(gmapdp_ctx* ctx, int code, const char* fmt, hipError_t e) {
@@ -525,6 +529,14 @@ static int fail(gmapdp_ctx* ctx, int code, const char* fmt, hipError_t e) {
 
 static int bad(gmapdp_ctx* ctx, const char* msg) {
   if (ctx) ctx->err = msg;
+  return GMAPDP_EINVAL;
+}
+
+// Only the nosimd single and end gaps run under an alternate-allele genome; every other family's entry points
+// refuse a context that has one bound, before any launch (0: none bound, go on).
+static int refuse_alt(gmapdp_ctx* ctx, const char* family) {
+  if (!ctx || !ctx->d_genome_alt) return 0;
+  ctx->err = std::string(family) + " does not run under an alternate-allele genome (gmapdp_set_genome_alt): unbind it first";
   return GMAPDP_EINVAL;
 }
 
@@ -611,6 +623,7 @@ void gmapdp_destroy(gmapdp_ctx* ctx) {
   ctx->d_cs.reset();
   ctx->d_isc.reset();
   ctx->d_genome.reset();
+  ctx->d_genome_alt.reset();
   for (int i = 0; i < gmapdp_ctx::kAux; i++) {
     if (ctx->aux[i]) (void)hipStreamSynchronize(ctx->aux[i]);
     if (ctx->aux[i]) (void)hipStreamDestroy(ctx->aux[i]);
@@ -679,6 +692,7 @@ int gmapdp_set_genome(gmapdp_ctx* ctx, const uint32_t* blocks, size_t nwords, ui
   if (!ctx || !blocks || nwords < (size_t)((length + 31) / 32) * 3) return GMAPDP_EINVAL;
   // coordinates are 64-bit (gmapdp_coord_t): gmapl genomes past 2^32 nt are supported
   (void)hipSetDevice(ctx->device);
+  ctx->d_genome_alt.reset();  // a new primary genome drops the alternate one
   hipError_t e = ctx->d_genome.alloc(nwords * sizeof(uint32_t));
   if (e != hipSuccess) return fail(ctx, GMAPDP_ENOMEM, "hipMalloc genome: %s", e);
   e = hipMemcpy(ctx->d_genome, blocks, nwords * sizeof(uint32_t), hipMemcpyHostToDevice);
@@ -687,6 +701,34 @@ int gmapdp_set_genome(gmapdp_ctx* ctx, const uint32_t* blocks, size_t nwords, ui
   ctx->genome_length = length;
   return GMAPDP_OK;
 }
+
+// The alternate-allele genome (gmap --use-snps' genomealt): the packed alternate sequence, position for
+// position beside the primary genome already bound.  The kernels read its high / low words only; 'N' comes
+// from the primary genome's flag words (uncompress_mmap_snps_subst, genome.c:9419).
+int gmapdp_set_genome_alt(gmapdp_ctx* ctx, const uint32_t* blocks, size_t nwords, uint64_t length) {
+  if (!ctx) return GMAPDP_EINVAL;
+  (void)hipSetDevice(ctx->device);
+  if (!blocks) {  // unbind
+    ctx->d_genome_alt.reset();
+    return GMAPDP_OK;
+  }
+  if (!ctx->d_genome) {
+    ctx->err = "alternate genome: no primary genome bound";
+    return GMAPDP_ENOGENOME;
+  }
+  if (nwords != ctx->genome_words || length != ctx->genome_length)
+    return bad(ctx, "alternate genome: length and word count must equal the primary genome's");
+  hipError_t e = ctx->d_genome_alt.alloc(nwords * sizeof(uint32_t));
+  if (e != hipSuccess) return fail(ctx, GMAPDP_ENOMEM, "hipMalloc alternate genome: %s", e);
+  e = hipMemcpy(ctx->d_genome_alt, blocks, nwords * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    ctx->d_genome_alt.reset();
+    return fail(ctx, GMAPDP_ENOMEM, "alternate genome upload: %s", e);
+  }
+  return GMAPDP_OK;
+}
+
+int gmapdp_has_genome_alt(const gmapdp_ctx* ctx) { return ctx && ctx->d_genome_alt ? 1 : 0; }
 
 int gmapdp_reserve(gmapdp_ctx* ctx, size_t bytes, int what) {
   if (!ctx) return GMAPDP_EINVAL;
@@ -751,9 +793,28 @@ void gmapdp_dgenome_destroy(gmapdp_dgenome* g) {
 int gmapdp_use_dgenome(gmapdp_ctx* ctx, const gmapdp_dgenome* g) {
   if (!ctx || !g || ctx->device != g->device) return GMAPDP_EINVAL;
   (void)hipSetDevice(ctx->device);
+  ctx->d_genome_alt.reset();  // a new primary genome drops the alternate one
   ctx->d_genome.view(g->d);
   ctx->genome_words = g->words;
   ctx->genome_length = g->length;
+  return GMAPDP_OK;
+}
+
+int gmapdp_use_dgenome_alt(gmapdp_ctx* ctx, const gmapdp_dgenome* g) {
+  if (!ctx) return GMAPDP_EINVAL;
+  (void)hipSetDevice(ctx->device);
+  if (!g) {  // unbind
+    ctx->d_genome_alt.reset();
+    return GMAPDP_OK;
+  }
+  if (ctx->device != g->device) return bad(ctx, "alternate genome: resident on another device");
+  if (!ctx->d_genome) {
+    ctx->err = "alternate genome: no primary genome bound";
+    return GMAPDP_ENOGENOME;
+  }
+  if (g->words != ctx->genome_words || g->length != ctx->genome_length)
+    return bad(ctx, "alternate genome: length and word count must equal the primary genome's");
+  ctx->d_genome_alt.view(g->d);
   return GMAPDP_OK;
 }
 
@@ -764,6 +825,9 @@ int gmapdp_share_genome(gmapdp_ctx* ctx, const gmapdp_ctx* owner) {
   ctx->d_genome.view(owner->d_genome);
   ctx->genome_words = owner->genome_words;
   ctx->genome_length = owner->genome_length;
+  // the owner's alternate genome too (none: this context's is dropped, as by any new primary genome)
+  if (owner->d_genome_alt) ctx->d_genome_alt.view(owner->d_genome_alt);
+  else ctx->d_genome_alt.reset();
   return GMAPDP_OK;
 }
 
@@ -851,6 +915,7 @@ int gmapdp_maxent_available(char* path, size_t path_bytes) {
 int gmapdp_maxent_sites(gmapdp_ctx* ctx, const gmapdp_coord_t* positions, const uint8_t* models,
                         const gmapdp_coord_t* chroffsets, size_t n, double* out) {
   if (!ctx || (n && (!positions || !models || !chroffsets || !out))) return GMAPDP_EINVAL;
+  if (const int rc_alt = refuse_alt(ctx, "gmapdp_maxent_sites")) return rc_alt;
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   if (n == 0) return GMAPDP_OK;
   (void)hipSetDevice(ctx->device);
@@ -876,6 +941,7 @@ int gmapdp_maxent_sites(gmapdp_ctx* ctx, const gmapdp_coord_t* positions, const 
 int gmapdp_canonical_links(gmapdp_ctx* ctx, const gmapdp_coord_t* prevpos, const gmapdp_coord_t* currpos, size_t n,
                            int plusp, gmapdp_coord_t chroffset, gmapdp_coord_t chrhigh, uint8_t* out) {
   if (!ctx || (n && (!prevpos || !currpos || !out))) return GMAPDP_EINVAL;
+  if (const int rc_alt = refuse_alt(ctx, "gmapdp_canonical_links")) return rc_alt;
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   if (n == 0) return GMAPDP_OK;
   (void)hipSetDevice(ctx->device);
@@ -1423,12 +1489,18 @@ static void class_work(ClassOf& c, const DevGenomeProblem& d) {
   c.gm = 0;
 }
 
-// one single / end gap's launch class (classify's rules)
-static ClassOf classify_dev(DevProblem& d, bool latency) {
+// one single / end gap's launch class (classify's rules).  alt: the context has an alternate-allele genome
+// bound: every nosimd problem takes the band layout's alternate-allele kernel (kDpAlt) -- no packed narrow
+// class, no rows layout, as in latency mode and with rows_disabled() -- and the SIMD semantics are refused.
+static ClassOf classify_dev(DevProblem& d, bool latency, bool alt) {
   ClassOf c{};
   c.pair = (size_t)d.rlength + (size_t)d.glength + 2;
   d.dirs_offset = 0;
   const bool nofill = d.kind != kSingle && d.endalign == kQueryendNogaps;
+  if (alt && (d.flags & kFSimd)) {
+    c.err = "GMAPDP_SIMD single / end gaps do not run under an alternate-allele genome (gmapdp_set_genome_alt)";
+    return c;
+  }
   if ((d.flags & kFSimd) && d.kind != kSingle) {
     // Dynprog_end5/3_gap of the SIMD builds (dynprog_end.c:1406 / 2027): 8-bit triangles when
     // either length is below use8p_size[ENDQ]
@@ -1454,7 +1526,7 @@ static ClassOf classify_dev(DevProblem& d, bool latency) {
   if (d.open > 0 && !nofill) { c.err = "positive gap-open penalty is not supported by the scan formulation"; return c; }
   if (d.lband < 0 || d.uband < 0) { c.err = "negative band"; return c; }
   const int W = d.lband + d.uband + 1;
-  if (!latency && (nofill || W <= 32)) {  // narrow band: pack 64/S problems per wave
+  if (!latency && !alt && (nofill || W <= 32)) {  // narrow band: pack 64/S problems per wave
     const int S = (nofill || W <= 16) ? 16 : 32;
     const size_t slot = slot_bucket(lds_slot_dpx(d.rlength, d.glength));
     if (slot && slot * (64 / S) + lds_dirs_dpx(d.glength) <= kLdsBudget) {
@@ -1467,17 +1539,18 @@ static ClassOf classify_dev(DevProblem& d, bool latency) {
   if (R > kMaxR) { c.err = "band wider than 4096"; return c; }
   // a band wider than the query: lanes over the query's rows cost fewer words per column
   const int Rrows = pick_R(d.rlength + 1);
-  const bool rows = !nofill && Rrows < R && !rows_disabled();
+  const bool rows = !nofill && Rrows < R && !rows_disabled() && !alt;
   if (rows) R = Rrows;
-  size_t lds = lds_bytes_dp(d.rlength, d.glength, R, !nofill);
+  size_t lds = lds_bytes_dp(d.rlength, d.glength, R, !nofill, alt);
   const bool dirs_lds = !nofill && lds <= kLdsBudget;
   if (!dirs_lds) {
-    lds = lds_bytes_dp(d.rlength, d.glength, R, false);
+    lds = lds_bytes_dp(d.rlength, d.glength, R, false, alt);
     if (!nofill) c.gdirs = ((size_t)(d.glength + 1) * 4 * R * 8 + 255) & ~(size_t)255;
   }
   if (lds > 160 * 1024) { c.err = "problem exceeds the LDS of a CU"; return c; }
   c.need = lds_bucket(lds);
-  c.key = class_key((int)(rows ? PlanCore::kDpRows : PlanCore::kDp), R, dirs_lds ? 1 : 0, latency ? 0 : c.need);
+  const int kind = alt ? PlanCore::kDpAlt : rows ? PlanCore::kDpRows : PlanCore::kDp;
+  c.key = class_key(kind, R, dirs_lds ? 1 : 0, latency ? 0 : c.need);
   return c;
 }
 
@@ -1524,6 +1597,8 @@ static int classify(gmapdp_ctx* ctx, PlanCore& plan) {
   // direction placement) with the LDS of its largest member, and no packed narrow-band kernels, so a
   // batch is a few launches whose latencies do not add up class after class.
   const bool latency = nd + ng <= latency_batch();
+  const bool alt = ctx->d_genome_alt != nullptr;
+  plan.alt = alt;
   PlanTimer tm("classify");
   // per problem (threads): its class; slots 0..nd-1 single / end gaps, nd.. genome gaps
   HostArray<ClassOf> cls(nd + ng);
@@ -1532,7 +1607,7 @@ static int classify(gmapdp_ctx* ctx, PlanCore& plan) {
     for (size_t s = lo; s < hi; s++) {
       ClassOf& c = cls[s];
       if (s < nd) {
-        c = classify_dev(plan.dev[s], latency);
+        c = classify_dev(plan.dev[s], latency, alt);
         if (!c.err) class_work(c, plan.dev[s]);
       } else {
         c = classify_gdev(plan.gdev[s - nd], latency, lds_dirs_max, rowfill);
@@ -1899,11 +1974,12 @@ static hipError_t launch_one(gmapdp_ctx* ctx, const PlanCore& plan, int li, cons
                       L.dirs_lds ? nullptr : (unsigned char*)ctx->gdirs.p + L.gdirs_offset, stream, a.d_probs,
                       a.d_order + L.first, ctx->d_genome, ctx->genome_words, a.d_q, a.d_quc, ctx->d_sc, ctx->d_cs,
                       a.d_results, a.d_pairs);
-  if (L.kind == PlanCore::kDp || L.kind == PlanCore::kDpRows)
+  if (L.kind == PlanCore::kDpAlt && !ctx->d_genome_alt) return hipErrorInvalidValue;  // (run_plan's callers check)
+  if (L.kind == PlanCore::kDp || L.kind == PlanCore::kDpRows || L.kind == PlanCore::kDpAlt)
     return launch_dp(L.R, L.dirs_lds, L.kind == PlanCore::kDpRows, L.count, L.lds, stream, a.d_probs,
                      a.d_order + L.first, ctx->d_genome,
                      ctx->genome_words, a.d_q, a.d_quc, ctx->d_sc, ctx->d_cs, a.d_results, a.d_pairs,
-                     (uint64_t*)ctx->gdirs.p);
+                     (uint64_t*)ctx->gdirs.p, L.kind == PlanCore::kDpAlt ? ctx->d_genome_alt.get() : nullptr);
   if (!a.d_gresults || !a.d_sprob) return hipErrorInvalidValue;
   // device MaxEnt: gg_kernel evaluates the models while it stages the segments (no me_gap_kernel prologue,
   // no probability arena written and read back); host probabilities: read from d_sprob
@@ -1954,6 +2030,8 @@ static int run_batch(gmapdp_ctx* ctx, const gmapdp_single_problem* singles, int 
   const int n = nsingle + nend;
   if (!ctx || n < 0 || ngenome < 0 || (n && !results) || (ngenome && !gresults)) return GMAPDP_EINVAL;
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
+  if (ngenome > 0)
+    if (const int rc = refuse_alt(ctx, "Dynprog_genome_gap")) return rc;
   if (n + ngenome == 0) return GMAPDP_OK;
   (void)hipSetDevice(ctx->device);
   PlanCore plan;
@@ -2281,6 +2359,7 @@ int gmapdp_cdna_gap_batch(gmapdp_ctx* ctx, const gmapdp_cdna_problem* problems, 
                           const char* qseq_uc, size_t qbytes, gmapdp_cdna_result* results, gmapdp_pair* pairs,
                           size_t pair_capacity) {
   if (!ctx || n < 0 || (n > 0 && (!problems || !results))) return GMAPDP_EINVAL;
+  if (const int rc_alt = refuse_alt(ctx, "Dynprog_cdna_gap")) return rc_alt;
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   if (n == 0) return GMAPDP_OK;
   (void)hipSetDevice(ctx->device);
@@ -2464,6 +2543,7 @@ int gmapdp_end_splicejunction_batch(gmapdp_ctx* ctx, const gmapdp_sj_problem* pr
                                     const char* qseq_uc, size_t qbytes, const char* jseq, size_t jbytes,
                                     gmapdp_sj_result* results, gmapdp_pair* pairs, size_t pair_capacity) {
   if (!ctx || n < 0 || (n > 0 && (!problems || !results))) return GMAPDP_EINVAL;
+  if (const int rc_alt = refuse_alt(ctx, "Dynprog_end5/3_splicejunction")) return rc_alt;
   if (n == 0) return GMAPDP_OK;
   (void)hipSetDevice(ctx->device);
   std::vector<DevSjProblem> dev;
@@ -2603,6 +2683,14 @@ static hipError_t plan_uploaded(const gmapdp_plan* p) {
   return e;
 }
 
+// A plan's launch classes depend on whether an alternate-allele genome was bound when it was made: it runs
+// only in a context whose binding is the same (bound or not) as then.
+static int plan_alt_mismatch(gmapdp_ctx* ctx, const gmapdp_plan* plan) {
+  if (plan->in.alt == (ctx->d_genome_alt != nullptr)) return 0;
+  return bad(ctx, plan->in.alt ? "plan made under an alternate-allele genome: the context has none bound now"
+                               : "plan made without an alternate-allele genome: the context has one bound now");
+}
+
 static RunArgs plan_args(const gmapdp_plan* plan, const char* d_qseq, const char* d_qseq_uc, gmapdp_result* d_results,
                          gmapdp_pair* d_pairs) {
   RunArgs a;
@@ -2629,6 +2717,8 @@ int gmapdp_plan_create_all(gmapdp_ctx* ctx, const gmapdp_single_problem* singles
   if (!ctx || !out || nsingle < 0 || nend < 0 || ngenome < 0 || nsingle + nend + ngenome <= 0) return GMAPDP_EINVAL;
   if ((nsingle && !singles) || (nend && !ends) || (ngenome && !genomes)) return GMAPDP_EINVAL;
   if ((nsingle + nend && !host_results) || (ngenome && !host_genome_results)) return GMAPDP_EINVAL;
+  if (ngenome > 0)
+    if (const int rc = refuse_alt(ctx, "Dynprog_genome_gap (plans with genome gaps)")) return rc;
   (void)hipSetDevice(ctx->device);
   gmapdp_plan* p = new gmapdp_plan();
   PlanTimer tm("plan_create_all");
@@ -2816,7 +2906,7 @@ int gmapdp_plan_launch_member_scratch(const gmapdp_plan* plan, int li, uint64_t*
     } else {
       DevProblem d = in.dev[in.order[L.first + k]];
       const uint64_t o = (uint64_t)d.dirs_offset;  // (classify_dev resets its copy's)
-      put(k, o, classify_dev(d, latency).gdirs);
+      put(k, o, classify_dev(d, latency, in.alt).gdirs);
     }
   }
   if (offset) *offset = hi ? lo : 0;
@@ -2835,6 +2925,7 @@ int gmapdp_plan_run(gmapdp_ctx* ctx, const gmapdp_plan* plan, const char* d_qseq
   if (!ctx || !plan) return GMAPDP_EINVAL;
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   if (!plan->in.gdev.empty() && (!plan->d_sprob || !plan->d_gresults)) return bad(ctx, "genome-gap buffers not bound");
+  if (const int rc = plan_alt_mismatch(ctx, plan)) return rc;
   if (const hipError_t eu = plan_uploaded(plan)) return fail(ctx, GMAPDP_ELAUNCH, "plan upload: %s", eu);
   return run_plan(ctx, plan->in, plan_args(plan, d_qseq, d_qseq_uc, d_results, d_pairs), stream_of(ctx, stream));
 }
@@ -2844,6 +2935,7 @@ static int plan_run_launch(gmapdp_ctx* ctx, const gmapdp_plan* plan, int li, con
                            bool prologue) {
   if (!ctx || !plan || li < 0 || li >= (int)plan->in.launches.size()) return GMAPDP_EINVAL;
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
+  if (const int rc = plan_alt_mismatch(ctx, plan)) return rc;
   if (plan->in.gdirs_bytes) {
     hipError_t e = ctx->gdirs.ensure(plan->in.gdirs_bytes);
     if (e != hipSuccess) return fail(ctx, GMAPDP_ENOMEM, "direction scratch: %s", e);
@@ -3255,6 +3347,7 @@ static int oligo_plan_build(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problem
                             size_t qbytes, std::unique_ptr<gmapdp_oligo_plan>& plan, bool split,
                             bool sizing = false) {
   plan.reset();
+  if (const int rc_alt = refuse_alt(ctx, "stage-2 seeding (gmapdp_oligo_*, gmapdp_stage2_*)")) return rc_alt;
   // stage 2 exists in STANDARD and the three stranded modes; GMAP itself refuses the non-stranded ones
   if (oi_reduction_of(ctx->mode, true) < 0)
     return bad(ctx, "stage 2 in a non-stranded cmet / atoi / ttoc mode (GMAP supports the stranded modes only)");
@@ -3372,6 +3465,7 @@ int gmapdp_oligo_plan_run(gmapdp_ctx* ctx, const gmapdp_oligo_plan* plan, const 
                           gmapdp_oligo_result* d_results, int32_t* d_npositions, int32_t* d_mappings,
                           uint32_t* d_positions, int32_t* d_diagonals, void* stream) {
   if (!ctx || !plan) return GMAPDP_EINVAL;
+  if (const int rc_alt = refuse_alt(ctx, "stage-2 seeding (gmapdp_oligo_*, gmapdp_stage2_*)")) return rc_alt;
   if (plan->mode != ctx->mode) return bad(ctx, "an oligo plan made by a context of another mode");
   if (plan->n == 0) return GMAPDP_OK;
   (void)hipSetDevice(ctx->device);
@@ -3405,6 +3499,7 @@ int gmapdp_oligo_mappings_batch(gmapdp_ctx* ctx, const gmapdp_oligo_problem* pro
                                 size_t diagonal_capacity) {
   if (!ctx || n < 0 || (n > 0 && (!problems || !results || !qseq_uc || !npositions || !mappings)))
     return GMAPDP_EINVAL;
+  if (const int rc_alt = refuse_alt(ctx, "stage-2 seeding (gmapdp_oligo_*)")) return rc_alt;
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   if (n == 0) return GMAPDP_OK;
   {
@@ -3505,6 +3600,7 @@ int gmapdp_scan_plan_create(gmapdp_ctx* ctx, const gmapdp_oligo_problem* problem
   *plan = nullptr;
   if (oi_reduction_of(ctx->mode, true) < 0)
     return bad(ctx, "stage 2 in a non-stranded cmet / atoi / ttoc mode (GMAP supports the stranded modes only)");
+  if (const int rc_alt = refuse_alt(ctx, "Stage2_scan (gmapdp_scan_plan_*)")) return rc_alt;
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   (void)hipSetDevice(ctx->device);
   OligoClasses C;
@@ -3602,6 +3698,7 @@ void gmapdp_scan_plan_destroy(gmapdp_scan_plan* plan) { delete plan; }
 int gmapdp_scan_plan_run(gmapdp_ctx* ctx, const gmapdp_scan_plan* plan, const char* d_qseq_uc,
                          gmapdp_scan_result* d_results, void* stream) {
   if (!ctx || !plan) return GMAPDP_EINVAL;
+  if (const int rc_alt = refuse_alt(ctx, "Stage2_scan (gmapdp_scan_plan_*)")) return rc_alt;
   if (plan->mode != ctx->mode) return bad(ctx, "a scan plan made by a context of another mode");
   if (plan->n == 0) return GMAPDP_OK;
   if (!d_qseq_uc || !d_results) return GMAPDP_EINVAL;
@@ -3729,6 +3826,7 @@ extern "C" int gmapdp_stage2_batch(gmapdp_ctx* ctx, const gmapdp_stage2_problem*
   if (!ctx || n < 0 || (n > 0 && (!problems || !results || !qseq || !qseq_uc))) return GMAPDP_EINVAL;
   if (paths_needed) *paths_needed = 0;
   if (pairs_needed) *pairs_needed = 0;
+  if (const int rc_alt = refuse_alt(ctx, "Stage2_compute (gmapdp_stage2_*)")) return rc_alt;
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   if (n == 0) return GMAPDP_OK;
   (void)hipSetDevice(ctx->device);
@@ -3834,6 +3932,7 @@ extern "C" int gmapdp_stage2x_batch(gmapdp_ctx* ctx, const gmapdp_stage2x_proble
   if (!ctx || n < 0 || (n > 0 && (!problems || !results || !qseq || !qseq_uc))) return GMAPDP_EINVAL;
   if (paths_needed) *paths_needed = 0;
   if (pairs_needed) *pairs_needed = 0;
+  if (const int rc_alt = refuse_alt(ctx, "Stage2_compute_one / _ends / _starts (gmapdp_stage2x_batch)")) return rc_alt;
   if (!ctx->d_genome) {
     ctx->err = "stage 2x: the context has no genome (gmapdp_set_genome)";
     return GMAPDP_ENOGENOME;
@@ -3903,6 +4002,7 @@ extern "C" int gmapdp_microexon_search(gmapdp_ctx* ctx, const gmapdp_microexon_p
                                        size_t cand_capacity, size_t* cands_needed) {
   if (!ctx || n < 0 || (n > 0 && (!problems || !results || !qseq || !qseq_uc))) return GMAPDP_EINVAL;
   if (cands_needed) *cands_needed = 0;
+  if (const int rc_alt = refuse_alt(ctx, "Dynprog_microexon_int (gmapdp_microexon_*)")) return rc_alt;
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   if (n == 0) return GMAPDP_OK;
   (void)hipSetDevice(ctx->device);
@@ -3980,6 +4080,7 @@ extern "C" int gmapdp_microexon_finish(gmapdp_ctx* ctx, const gmapdp_microexon_p
                                        size_t ncands, gmapdp_microexon_result* results, gmapdp_pair* pairs,
                                        size_t pair_capacity) {
   if (!ctx || n < 0 || (n > 0 && (!problems || !results || !qseq || !qseq_uc))) return GMAPDP_EINVAL;
+  if (const int rc_alt = refuse_alt(ctx, "Dynprog_microexon_int (gmapdp_microexon_*)")) return rc_alt;
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   if (n == 0) return GMAPDP_OK;
   if (ncands && !candidates) return GMAPDP_EINVAL;
@@ -4067,6 +4168,7 @@ extern "C" int gmapdp_mixed_batch(gmapdp_ctx* ctx, const char* qseq, const char*
       (nxf && (!m->finishes || !m->finish_results)) || (nxw && (!m->wholes || !m->whole_results)))
     return GMAPDP_EINVAL;
   m->candidates_needed = 0;
+  if (const int rc_alt = refuse_alt(ctx, "gmapdp_mixed_batch")) return rc_alt;
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   if (nsingle + nend + ngenome + nxs + nxf + nxw == 0) return GMAPDP_OK;
   if (!qseq || !qseq_uc) return GMAPDP_EINVAL;
@@ -4358,6 +4460,7 @@ extern "C" int gmapdp_microexon_plan_create(gmapdp_ctx* ctx, const gmapdp_microe
                                             gmapdp_microexon_plan** plan) {
   if (!ctx || !plan || n < 0 || (n > 0 && (!problems || !qseq || !qseq_uc))) return GMAPDP_EINVAL;
   *plan = nullptr;
+  if (const int rc_alt = refuse_alt(ctx, "Dynprog_microexon_int (gmapdp_microexon_*)")) return rc_alt;
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   std::vector<gmapdp_microexon_result> res(std::max(n, 1));
   size_t need = 0;
@@ -4399,6 +4502,7 @@ extern "C" int gmapdp_microexon_plan_run(gmapdp_ctx* ctx, const gmapdp_microexon
                                          gmapdp_microexon_result* d_results, gmapdp_pair* d_pairs, int what,
                                          void* stream) {
   if (!ctx || !plan || !d_results) return GMAPDP_EINVAL;
+  if (const int rc_alt = refuse_alt(ctx, "Dynprog_microexon_int (gmapdp_microexon_*)")) return rc_alt;
   if (plan->n == 0) return GMAPDP_OK;
   if ((what & 2) && !d_pairs) return GMAPDP_EINVAL;
   (void)hipSetDevice(ctx->device);
@@ -4489,6 +4593,7 @@ int gmapdp_stage2_plan_create(gmapdp_ctx* ctx, const gmapdp_stage2_problem* prob
                               const char* qseq_uc, size_t qbytes, gmapdp_stage2_plan** plan) {
   if (!ctx || !plan || n <= 0 || !problems || !qseq || !qseq_uc) return GMAPDP_EINVAL;
   *plan = nullptr;
+  if (const int rc_alt = refuse_alt(ctx, "Stage2_compute (gmapdp_stage2_*)")) return rc_alt;
   if (!ctx->d_genome) return GMAPDP_ENOGENOME;
   (void)hipSetDevice(ctx->device);
   const double* canon_metab = nullptr;
@@ -4568,6 +4673,7 @@ int gmapdp_stage2_plan_create(gmapdp_ctx* ctx, const gmapdp_stage2_problem* prob
 int gmapdp_stage2_plan_run(gmapdp_ctx* ctx, const gmapdp_stage2_plan* plan, const char* d_qseq, const char* d_qseq_uc,
                            gmapdp_stage2_result* d_results, int what, void* stream) {
   if (!ctx || !plan || !d_qseq || !d_qseq_uc || !d_results) return GMAPDP_EINVAL;
+  if (const int rc_alt = refuse_alt(ctx, "Stage2_compute (gmapdp_stage2_*)")) return rc_alt;
   (void)hipSetDevice(ctx->device);
   // what: 1 seeding, 2 chaining; or one chaining kernel alone over a previous run's scratch: 4 s2a, 8 s2b, 16 s2c
   const int chain = (what & 2) ? 7 : ((what >> 2) & 7);
@@ -4577,6 +4683,7 @@ int gmapdp_stage2_plan_run(gmapdp_ctx* ctx, const gmapdp_stage2_plan* plan, cons
 int gmapdp_stage2_plan_seeding_results(gmapdp_ctx* ctx, const gmapdp_stage2_plan* plan, void* stream,
                                        gmapdp_oligo_result* out) {
   if (!ctx || !plan || !out) return GMAPDP_EINVAL;
+  if (const int rc_alt = refuse_alt(ctx, "Stage2_compute (gmapdp_stage2_*)")) return rc_alt;
   (void)hipSetDevice(ctx->device);
   hipStream_t s = stream_of(ctx, stream);
   hipError_t e = hipMemcpyAsync(out, plan->d_ores, sizeof(gmapdp_oligo_result) * plan->n, hipMemcpyDeviceToHost, s);
@@ -4600,6 +4707,7 @@ int gmapdp_stage2_plan_fetch(gmapdp_ctx* ctx, const gmapdp_stage2_plan* plan, co
   if (!ctx || !plan || !d_results || !results) return GMAPDP_EINVAL;
   if (paths_needed) *paths_needed = 0;
   if (pairs_needed) *pairs_needed = 0;
+  if (const int rc_alt = refuse_alt(ctx, "Stage2_compute (gmapdp_stage2_*)")) return rc_alt;
   (void)hipSetDevice(ctx->device);
   hipStream_t s = stream_of(ctx, stream);
   unsigned long long cnt[4] = {0, 0, 0, 0};
@@ -4621,6 +4729,7 @@ size_t gmapdp_stage2_plan_compact_bound(const gmapdp_stage2_plan* plan, size_t* 
 int gmapdp_stage2_plan_compact_pairs(gmapdp_ctx* ctx, const gmapdp_stage2_plan* plan, uint8_t* d_out,
                                      uint64_t* d_offsets, void* stream) {
   if (!ctx || !plan || !d_offsets) return GMAPDP_EINVAL;
+  if (const int rc_alt = refuse_alt(ctx, "Stage2_compute (gmapdp_stage2_*)")) return rc_alt;
   return gmapdp_compact_path_pairs(ctx, plan->d_paths, (const uint64_t*)(plan->d_counters + 1), plan->path_cap,
                                    plan->d_pairs, plan->pair_cap, d_out, d_offsets, stream);
 }

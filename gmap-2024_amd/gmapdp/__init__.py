@@ -229,6 +229,9 @@ def load_library(path=LIB_PATH):
                                            C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
         "gmapdp_pack_genome": (C.c_int, [C.c_char_p, C.c_uint64, C.c_void_p]),
         "gmapdp_set_genome": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64]),
+        "gmapdp_set_genome_alt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64]),
+        "gmapdp_use_dgenome_alt": (C.c_int, [C.c_void_p, C.c_void_p]),
+        "gmapdp_has_genome_alt": (C.c_int, [C.c_void_p]),
         "gmapdp_single_gap_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                               C.c_void_p, C.c_void_p, C.c_size_t]),
         "gmapdp_single_pair_capacity": (C.c_size_t, [C.c_void_p, C.c_int]),
@@ -476,6 +479,26 @@ class Engine:
         blocks = np.ascontiguousarray(blocks, dtype=np.uint32)
         self._check(self.lib.gmapdp_set_genome(self.h, blocks.ctypes.data, blocks.size, length), "gmapdp_set_genome")
         self.genome_length = length
+
+    def set_genome_alt(self, seq: bytes = None, blocks: np.ndarray = None):
+        """Bind the alternate-allele genome (gmap --use-snps' genomealt; gmapdp_set_genome_alt): the alternate
+        sequence, or its packed blocks, as long as the primary genome bound already.  Single and end gaps then
+        run under it (each pair's genomealt is the alternate allele); every other family is refused until
+        clear_genome_alt().  A new primary genome drops it."""
+        if blocks is None:
+            blocks = pack_genome(seq)
+            length = len(seq)
+        else:
+            length = self.genome_length
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint32)
+        self._check(self.lib.gmapdp_set_genome_alt(self.h, blocks.ctypes.data, blocks.size, length),
+                    "gmapdp_set_genome_alt")
+
+    def clear_genome_alt(self):
+        self._check(self.lib.gmapdp_set_genome_alt(self.h, None, 0, 0), "gmapdp_set_genome_alt")
+
+    def has_genome_alt(self):
+        return bool(self.lib.gmapdp_has_genome_alt(self.h))
 
     # -- batched Dynprog_single_gap ------------------------------------------
     @staticmethod

@@ -27,8 +27,9 @@
  * (HAVE_SSE2: gmap.sse42 / .avx2 / .avx512, dynprog_simd.c) gets GMAPDP_SIMD on
  * every call, a nosimd build the Dynprog_standard semantics.
  *
- * Scope (the engine's, include/gmapdp.h): no alternate-
- * allele genome (genomealt must equal genome); Dynprog_T created with
+ * Scope: no alternate-allele genome (genomealt must equal genome: the engine
+ * runs single and end gaps under one, gmapdp_set_genome_alt, but no other
+ * family, so GMAP as a whole cannot); Dynprog_T created with
  * gmap.c's defaults (max_rlength 660, max_glength 2000); homopolymer mode
  * off; no splicing IIT in Dynprog_genome_gap.  Anything else is refused with
  * a message and abort() -- there is no silent CPU fallback.
@@ -475,7 +476,8 @@ shim_known_sites (uint8_t *left_known, uint8_t *right_known, int glengthL, int g
 /* Refusals that depend on the caller's Dynprog_T / genomes (checked on the calling thread). */
 static void
 shim_check_call (Genome_T genome, Genome_T genomealt, Dynprog_T dynprog) {
-  if (genomealt != NULL && genomealt != genome) shim_refuse("an alternate-allele genome (genomealt)");
+  if (genomealt != NULL && genomealt != genome) shim_refuse("an alternate-allele genome (genomealt; the engine runs only single and end gaps under one, "
+                                                             "gmapdp_set_genome_alt)");
   if (dynprog != NULL && (dynprog->max_rlength != GMAPDP_MAX_RLENGTH || dynprog->max_glength != GMAPDP_MAX_GLENGTH))
     shim_refuse("a Dynprog_T with non-default maximum lengths");
 }

@@ -943,6 +943,37 @@ int gmapdp_pack_genome (const char *seq, uint64_t length, uint32_t *blocks);
  * 2^32 nt or more (gmapl, 64-bit Univcoord_T) are GMAPDP_EINVAL. */
 int gmapdp_set_genome (gmapdp_ctx *ctx, const uint32_t *blocks, size_t nwords, uint64_t length);
 
+/* The alternate-allele genome (GMAP run with --use-snps hands every Dynprog_* entry a second Genome_T,
+ * genomealt).  `blocks`: gmapdp_pack_genome of the alternate sequence, or GMAP's Genome_blocks(genomealt);
+ * position for position beside the primary genome, which must be bound already with the same `length` and
+ * `nwords` (GMAPDP_ENOGENOME without one, GMAPDP_EINVAL when they differ).  The engine reads the alternate
+ * genome's high / low words only: 'N' goes where the PRIMARY genome's flag bit is set, as in the reference
+ * (uncompress_mmap_snps_subst, Genome_get_char).  blocks == NULL unbinds it.  Binding a new primary genome
+ * (gmapdp_set_genome, gmapdp_use_dgenome, gmapdp_share_genome) drops the alternate one;
+ * gmapdp_share_genome shares the owner's alternate genome as well.
+ *
+ * While an alternate genome is bound:
+ *  - nosimd Dynprog_single_gap / Dynprog_end5_gap / Dynprog_end3_gap run under it, bit-exact to the
+ *    reference's nosimd build: a cell scores the larger table entry of the two alleles, a pair is a match
+ *    through either allele, else ambiguous when either is consistent, else a mismatch, and every
+ *    gmapdp_pair carries genomealt.  Entry points: gmapdp_single_gap_batch, gmapdp_end_gap_batch,
+ *    gmapdp_dynprog_batch with ngenome == 0, gmapdp_plan_create / _plan_single / _plan_create_all without
+ *    genome gaps, and gmapdp_plan_run / _plan_run_launch on such plans.  Every problem takes the band
+ *    layout's alternate-allele kernel, one wave each (no packed narrow class, no rows layout).
+ *  - everything else is GMAPDP_EINVAL before any launch, with gmapdp_last_error naming the family:
+ *    GMAPDP_SIMD single / end problems; genome gaps (gmapdp_genome_gap_batch, _batch_known,
+ *    gmapdp_dynprog_batch and plans with genome gaps); gmapdp_cdna_gap_batch;
+ *    gmapdp_end_splicejunction_batch; gmapdp_microexon_*; gmapdp_mixed_batch; gmapdp_maxent_sites;
+ *    gmapdp_canonical_links; gmapdp_oligo_*, gmapdp_scan_plan_*, gmapdp_stage2_scan_batch,
+ *    gmapdp_stage2_* and gmapdp_stage2x_batch.
+ * A plan remembers whether it was made under an alternate genome: running it in a context whose binding
+ * (bound or not) differs from then is GMAPDP_EINVAL.  A context without one behaves exactly as before. */
+int gmapdp_set_genome_alt (gmapdp_ctx *ctx, const uint32_t *blocks, size_t nwords, uint64_t length);
+/* The same from an HBM-resident genome, no copy (g == NULL unbinds). */
+int gmapdp_use_dgenome_alt (gmapdp_ctx *ctx, const gmapdp_dgenome *g);
+/* 1 when an alternate genome is bound, else 0. */
+int gmapdp_has_genome_alt (const gmapdp_ctx *ctx);
+
 /* Run n Dynprog_single_gap problems.  Host arrays in, host arrays out
  * (the engine stages them through pinned device buffers).  `pairs` must
  * have room for gmapdp_single_pair_capacity(problems, n) records; result
